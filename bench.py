@@ -25,7 +25,16 @@ bytes / the max-over-ranks time per step.
 
 Algorithmic bytes per SpMV: 8*nnz + 4*(rows+1) + 4*cols + 8*rows.
 
-Also on the same JSON line:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs:
+it builds the matrices, runs the W warm-up steps, times the K steps and prints the JSON
+line (metric, value, ms_per_step, config, and a roofline entry taken from the HIP events
+around the timed steps themselves).  `--dump-outputs DIR` also writes what the last timed
+step computed -- the y its caller receives -- as DIR/y.npy (float32; DIR/y_rank<r>.npy per
+rank at N > 1), before anything else touches y; above 60 MB a fixed, seeded sample of its
+entries.  The inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
+
+With `--full`, also on the same JSON line (each leg has its `--no-*` switch):
   roofline      the dominant kernel: algorithmic bytes / SpMV time vs 8 TB/s.  N = 1:
                 HIP events around the replay of the captured graph of the K timed
                 SpMVs (per-SpMV time incl. the gaps between kernels), and the same
@@ -180,6 +189,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the per-SpMV distributions, the fp32-values, "
+                         "SpMM, R-MAT and config-5 legs and the CPU baselines (see the --no-* switches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the y of the last timed step to DIR/y.npy (float32; above 60 MB a "
+                         "fixed, seeded sample of its entries)")
     ap.add_argument("--workload", choices=("config2", "config5"), default="config2")
     ap.add_argument("--rows-per-rank", type=int, default=1 << 20, help="config2")
     ap.add_argument("--global-rows", type=int, default=1 << 26, help="config5")
@@ -217,6 +232,8 @@ def main():
     ap.add_argument("--no-fp32-values", action="store_true",
                     help="skip roofline.fp32_values (config 2 with arbitrary fp32 values)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` outside a launcher: start the N ranks ourselves (one
@@ -286,8 +303,9 @@ def main():
         if world == 1 and emu == 1 and args.workload == "config5":
             x_full = torch.rand(C, generator=g, device=dev) * 2 - 1
         y = torch.rand(R, generator=g, device=dev) * 2 - 1
-        reps.append(dict(M=M, rp=rp if k == 0 else None, ci=ci if k == 0 else None,
-                         va=va if k == 0 else None, x_local=x_local, x_full=x_full, y=y))
+        keep = args.full and k == 0   # the CSR arrays: the fp32-values leg and the CPU baseline
+        reps.append(dict(M=M, rp=rp if keep else None, ci=ci if keep else None,
+                         va=va if keep else None, x_local=x_local, x_full=x_full, y=y))
         del rp, ci, va
     build_s = time.perf_counter() - t_build0
     nnz = R * per
@@ -407,9 +425,16 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = bytes_rank * world / (elapsed / args.steps) / 1e9
 
-    # ---- distributions, outside the timed region ----------------------------------
+    if args.dump_outputs:   # before any further product updates y in place
+        dump_outputs(args.dump_outputs, torch, "y" if world == 1 else f"y_rank{rank}",
+                     reps[(args.warmup + args.steps - 1) % len(reps)]["y"])
+
+    # ---- distributions, outside the timed region (--full) -------------------------
     dist_info = {}
-    if use_graph:
+    if not args.full:
+        # the HIP events around the timed steps themselves: no run of its own
+        kern_ms = region_ms / args.steps
+    elif use_graph:
         per_replay = []
         for _ in range(max(1, args.replays)):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -420,8 +445,9 @@ def main():
             per_replay.append(a.elapsed_time(b) / args.steps)
         dist_info["graph_replay_ms_per_spmv"] = stats([region_ms / args.steps] + per_replay)
         kern_ms = float(np.median([region_ms / args.steps] + per_replay))
-    xs_local = None
-    if world == 1:
+    if not args.full:
+        pass   # a plain run ends with the timed steps
+    elif world == 1:
         def one(i):
             r = reps[i % len(reps)]
             r["M"].spmv(r["x_full"], r["y"], 1.0, 0.5, algo=args.algo)
@@ -472,14 +498,15 @@ def main():
             "kernel": KERNELS.get(layout, layout), "layout": layout,
             "xband_slabs": info["xband_slabs"], "xband_block_rows": info["xband_block_rows"],
             "kernel_ms": round(kern_ms, 5),
-            "kernel_ms_source": ("median over graph replays (per SpMV incl. inter-kernel gaps)"
+            "kernel_ms_source": ("HIP events around the timed steps (per step)" if not args.full else
+                                 "median over graph replays (per SpMV incl. inter-kernel gaps)"
                                  if use_graph else "median of per-launch HIP events"),
             "alg_bytes_per_launch": bytes_rank, "distribution": dist_info}
 
     # ---- config 2 with arbitrary fp32 values (rank 0, N = 1), right after the headline, in
     # the same chip state (after the R-MAT leg it measured 3 us slower) ----
-    if (world == 1 and emu == 1 and args.workload == "config2" and not args.no_fp32_values
-            and reps[0]["rp"] is not None):
+    if (args.full and world == 1 and emu == 1 and args.workload == "config2"
+            and not args.no_fp32_values and reps[0]["rp"] is not None):
         try:
             roof["fp32_values"] = fp32_values_line(args, torch, reps, R, C, bytes_rank, dev, dev_index)
         except Exception as exc:  # noqa: BLE001
@@ -487,7 +514,7 @@ def main():
 
     # ---- SpMM (config 3) on replica 0 -----------------------------------------------
     spmm = None
-    if not args.no_spmm and args.workload == "config2":
+    if args.full and not args.no_spmm and args.workload == "config2":
         N = args.spmm_n
         r0 = reps[0]
         g = torch.Generator(device=dev).manual_seed(3)
@@ -542,7 +569,8 @@ def main():
     # ---- R-MAT (config 4) on rank 0 at N = 1 ----------------------------------------
     rmat = None
     rmat_host = None
-    if world == 1 and emu == 1 and rank == 0 and not args.no_rmat and args.workload == "config2":
+    if (args.full and world == 1 and emu == 1 and rank == 0 and not args.no_rmat
+            and args.workload == "config2"):
         try:   # a failure here must not cost the config-2 line
             torch.cuda.synchronize()
             t_b = time.perf_counter()
@@ -617,7 +645,7 @@ def main():
 
     # ---- config 5: 2^26 x 2^26 strong scaling over the job's ranks ------------------
     config5 = None
-    if args.workload == "config2" and emu == 1 and not args.no_config5:
+    if args.full and args.workload == "config2" and emu == 1 and not args.no_config5:
         if ctx is not None:   # the config-2 products are done with: make room
             ctx.close()
             ctx = None
@@ -633,7 +661,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1) --------------------------------------------
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu and reps[0]["rp"] is not None:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu and reps[0]["rp"] is not None:
         cpu = cpu_baseline(args, reps[0], bytes_rank, rmat_host)
 
     if rank == 0:
@@ -663,6 +691,22 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # a dump stays under 64 MB, file header included
+DUMP_SAMPLE = 1 << 23            # entries kept of a longer y (32 MiB)
+
+
+def dump_outputs(out_dir: str, torch, name: str, y) -> None:
+    """y as out_dir/<name>.npy in float32; above DUMP_LIMIT_BYTES the DUMP_SAMPLE entries at
+    a fixed, seeded, ascending set of indices (the same set for the same length)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    n = int(y.numel())
+    if 4 * n > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        y = y[torch.from_numpy(idx).to(y.device)]
+    np.save(os.path.join(out_dir, name + ".npy"), y.detach().cpu().numpy().astype(np.float32, copy=False))
 
 
 def fp32_values_line(args, torch, reps, R, C, bytes_rank, dev, dev_index) -> dict:

@@ -18,14 +18,14 @@ if [[ $STEPS == all || $STEPS == *smoke* ]]; then
   tail -1 "$OUT/smoke.log"
 fi
 if [[ $STEPS == all || $STEPS == *bench* ]]; then
-  run timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; exit 13; }
+  run timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; exit 13; }
   tail -1 "$OUT/bench.log"
 fi
 if [[ $STEPS == all || $STEPS == *prof* ]]; then
   export TMPDIR=/tmp
   rm -rf "$OUT/prof"
   ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-      python3 "$ROOT/bench.py" --steps 50 --warmup 5 --no-cpu ) > "$OUT/prof.log" 2>&1 || { tail -30 "$OUT/prof.log"; exit 14; }
+      python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 --no-cpu ) > "$OUT/prof.log" 2>&1 || { tail -30 "$OUT/prof.log"; exit 14; }
   find "$OUT/prof" -name '*stats*' | head
 fi
 echo "gpu_check done"

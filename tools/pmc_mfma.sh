@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp || exit 1
 CTR="SQ_INSTS_VALU_MFMA_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE"
-timeout -s KILL 240 rocprofv3 --pmc $CTR --kernel-trace --output-format csv -d "$OUT/g1" -o run -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 --replays 1 --no-cpu --no-rmat --no-config5 --no-fp32-values > "$OUT/g1.log" 2>&1 || { tail -20 "$OUT/g1.log"; exit 31; }
+timeout -s KILL 240 rocprofv3 --pmc $CTR --kernel-trace --output-format csv -d "$OUT/g1" -o run -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 1 --replays 1 --no-cpu --no-rmat --no-config5 --no-fp32-values > "$OUT/g1.log" 2>&1 || { tail -20 "$OUT/g1.log"; exit 31; }
 python3 - "$OUT" "$ROOT/gpurun_out" ${KERNELS:-spmm_rowpanel2 spmm_mfma} <<'PY'
 import csv, glob, json, sys
 from collections import defaultdict
