@@ -32,6 +32,11 @@
  * SM_SERIAL_ROW_MAX terms and uses a tree sum for longer rows.  The bound for
  * every non-exact case is |y - y_ref| <= 1e-6 * sum|terms|.
  *
+ * Operands: any 4-byte aligned x / y / X / Y / a / c and any ld >= the row length; placement
+ * only selects the kernel (band layouts need x at 16 bytes, the row-panel SpMM ld % 4 == 0 and
+ * X, Y at 16 bytes, SM_ALGO_MFMA 8 bytes), and nothing outside y[0, n) or inside the padding
+ * columns [n_rhs, ld) is ever written ("Operand placement").
+ *
  * Concurrency: calls on one matrix from several streams or threads are correct;
  * SpMVs that use the matrix's scratch take turns on the device.
  *

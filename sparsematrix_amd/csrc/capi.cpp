@@ -1502,7 +1502,9 @@ sm_status sm_create_from_csr_device_ex(int64_t n_rows, int64_t n_cols, int64_t n
                         m->opts.sell_sigma == 0 && m->opts.sell_streams <= 1 && m->opts.exact_sell != 1;
     // The gathered chunk bands on the device (builddev_gcb.hip; config 5: 15 s on the host path).
     // Declined (a row's columns not ascending, size limits): the host path below decides.
-    if (dev_ok && xband && xband_kind_setting(m.get()) == kXbGcb) {
+    // A forced column relabeling (relabel = 1) is built beside the bands by the host path
+    // only, so the device path is declined there too: the same bytes either way.
+    if (dev_ok && xband && xband_kind_setting(m.get()) == kXbGcb && m->opts.relabel != 1) {
         hipError_t eb = hipSuccess;
         int rows_log2 = 0;
         int32_t slabs = 1;

@@ -42,6 +42,71 @@ def bits(a) -> np.ndarray:
     return np.ascontiguousarray(a, np.float32).reshape(-1).view(np.uint32)
 
 
+GUARD_BITS = 0x7FC0DEAD   # a quiet NaN no kernel computes: guard words and padding columns
+
+
+def _guarded_parent(n_elems: int):
+    torch = torch_dev()
+    parent = torch.empty(n_elems, dtype=torch.float32, device="cuda")
+    parent.view(torch.int32).fill_(GUARD_BITS)
+    assert parent.data_ptr() % 256 == 0, "allocation base not 256-byte aligned"
+    return parent
+
+
+def placed(vec, off: int, guard: int = 8):
+    """(view, parent): `vec` on the device at `off` floats past 16-byte alignment, between
+    `guard` words of GUARD_BITS on each side (off in 0..3, guard a multiple of 4)."""
+    torch = torch_dev()
+    v = np.ascontiguousarray(vec, np.float32).reshape(-1)
+    parent = _guarded_parent(guard + off + v.size + guard)
+    view = parent[guard + off: guard + off + v.size]
+    view.copy_(torch.from_numpy(v))
+    assert view.data_ptr() % 16 == 4 * off
+    return view, parent
+
+
+def _guard_words(parent) -> np.ndarray:
+    torch = torch_dev()
+    torch.cuda.synchronize()
+    return parent.view(torch.int32).cpu().numpy().view(np.uint32)
+
+
+def assert_guards(parent, off: int, n: int, guard: int = 8):
+    """Every guard word before and after placed()'s view still holds GUARD_BITS."""
+    w = _guard_words(parent)
+    lo, hi = guard + off, guard + off + n
+    assert w.size == hi + guard
+    bad = np.flatnonzero(np.concatenate([w[:lo], w[hi:]]) != GUARD_BITS)
+    assert bad.size == 0, f"guard words overwritten (index in front+back guards: {bad[:8].tolist()})"
+
+
+def placed_2d(mat, ld: int, off: int, guard: int = 8):
+    """(view, parent): the rows x n matrix `mat` as a row-major view of leading dimension
+    `ld` >= n starting `off` floats past 16-byte alignment; the padding columns [n, ld) and
+    `guard` words on each side hold GUARD_BITS."""
+    torch = torch_dev()
+    a = np.ascontiguousarray(mat, np.float32)
+    rows, n = a.shape
+    assert ld >= n
+    parent = _guarded_parent(guard + off + rows * ld + guard)
+    full = parent[guard + off: guard + off + rows * ld].view(rows, ld)
+    view = full[:, :n]
+    view.copy_(torch.from_numpy(a))
+    assert view.data_ptr() % 16 == 4 * off and view.stride(0) == ld
+    return view, parent
+
+
+def assert_guards_2d(parent, off: int, rows: int, n: int, ld: int, guard: int = 8):
+    """The guards and the padding columns [n, ld) of placed_2d()'s parent are bit-unchanged."""
+    w = _guard_words(parent)
+    lo, hi = guard + off, guard + off + rows * ld
+    assert w.size == hi + guard
+    assert (w[:lo] == GUARD_BITS).all() and (w[hi:] == GUARD_BITS).all(), "guard words overwritten"
+    pad = w[lo:hi].reshape(rows, ld)[:, n:]
+    bad = np.argwhere(pad != GUARD_BITS)
+    assert bad.size == 0, f"padding columns written, first (row, pad column): {bad[:4].tolist()}"
+
+
 def uniform_csr(n_rows: int, n_cols: int, per_row: int, seed: int, table=None):
     """`per_row` distinct sorted columns per row, values from a 255-entry table."""
     rng = np.random.default_rng(seed)

@@ -170,6 +170,29 @@ def test_devbuild_gcb_uniform(sm, n_rows, n_cols, per_row, slabs):
     _gcb_spmv_check(D, H, info, rp, ci, va, n_rows, n_cols, 3)
 
 
+def test_devbuild_gcb_forced_relabel(sm):
+    """layout "gcb" with relabel = 1 from a device CSR.  The host build adds the
+    column relabeling beside the bands (col_relabel == 1); the device gcb builder has none, so it
+    is declined for this combination and host_build 0 / 1 give the same bytes and info; the stream
+    kernel (the one that reads the relabeled columns) gives the same bits on both."""
+    from gpu_util import uniform_csr
+    torch = torch_dev()
+    n_rows, n_cols, per_row = 9000, 70001, 40
+    rp, ci, va = uniform_csr(n_rows, n_cols, per_row, seed=n_rows + n_cols)
+    D, H, info, _, _ = _both_gcb(sm, rp, ci, va, n_cols, dict(layout="gcb", relabel=1))
+    assert info["has_xband"] == 6 and info["col_relabel"] == 1, info
+    _gcb_spmv_check(D, H, info, rp, ci, va, n_rows, n_cols, 3)
+    x = np.random.default_rng(7).uniform(-1, 1, n_cols).astype(np.float32)
+    y0 = np.random.default_rng(8).uniform(-1, 1, n_rows).astype(np.float32)
+    xd = torch.from_numpy(x).cuda()
+    yd, yh = torch.from_numpy(y0).cuda(), torch.from_numpy(y0).cuda()
+    D.spmv(xd, yd, 1.3, 0.5, algo="stream")
+    H.spmv(xd, yh, 1.3, 0.5, algo="stream")
+    assert torch.equal(yd.view(torch.int32), yh.view(torch.int32))
+    want = oracle.csr_spmv(rp, ci, va, x, y0, 1.3, 0.5)   # 40-term rows: the reference's order
+    assert np.array_equal(bits(to_host(yd)), bits(want))
+
+
 def test_devbuild_gcb_long_segments_hub_columns(sm):
     """Rows of 90 consecutive columns (cut inside the run: a band holds at most 63 terms of a
     row), two hub columns in every row (a column's rows split over several bands)."""
