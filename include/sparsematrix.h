@@ -10,7 +10,9 @@
  * fp32 values), so m = 1 is the SpMV  y = alpha*B*x + beta*y  and a panel of
  * N right-hand sides is the SpMM  Y = alpha*B*X + beta*Y  (X: k x N, Y: n x N,
  * both row-major).  sm_num_rows/sm_num_cols report the reference's S view
- * (rows_ = k, cols_ = n; sparse-matrix.h:39-40).
+ * (rows_ = k, cols_ = n; sparse-matrix.h:39-40).  The other orientation,
+ * y = alpha*B^T*x + beta*y  (the reference's  C = alpha*A*S^T + beta*C), is the same
+ * product on the matrix sm_create_transpose builds from a held one.
  *
  * Semantics kept from the reference (SURVEY.md §7 "Drop-in semantics"):
  *   - beta is applied by multiplication whenever beta != 1 (so beta = 0
@@ -286,6 +288,24 @@ SM_API sm_status sm_create_from_csr_device_ex(int64_t n_rows, int64_t n_cols, in
                                               sm_stream stream, const sm_build_opts *opts,
                                               sm_matrix **out);
 
+/* A new matrix holding B^T of `src` (n_cols x n_rows; the reference view S^T: s_rows/s_cols
+ * swapped), transposed on src's device from its device CSR; layouts per `opts` (NULL: as the
+ * constructors choose).  Synchronises `stream`.  `src` is only read: concurrent products on
+ * it are fine.
+ * Row c of B^T holds the terms of column c of B by ascending source row, equal rows in stored
+ * order (a stable sort by column); values bit for bit.  The result is an ordinary matrix (every
+ * algorithm and layout; it holds a second copy of the terms).  A source built from the dense
+ * index hands on its codebook and the dense-index constructors' default options, so the result
+ * is what CopyForm builds from the same index with the other `trans`; no reference stream is
+ * kept (sm_build_ref_stream adds it; given the source's codebook it uses the ids the index gave
+ * the terms, which the result keeps at one byte per term -- equal codebook entries stay apart,
+ * the stream is the reference's own byte for byte).  Scratch while building: 24 bytes per term.
+ * A dense-index source costs more: its ids are read back from its reference stream on the host
+ * (one O(nnz) walk, a row_ptr download, an id upload) and sorted in a second pass of the same
+ * kernels, 32 bytes of scratch per term (+ 1 for the source's ids). */
+SM_API sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts,
+                                     sm_stream stream, sm_matrix **out);
+
 /* Destroy: sparse-matrix.cc:9-18 (frees host and device storage). */
 SM_API void sm_destroy(sm_matrix *m);
 
@@ -320,7 +340,9 @@ SM_API sm_status sm_copy_ref_stream(const sm_matrix *m, uint8_t *pos, uint8_t *v
  * comparison and SM_ALGO_NATIVE serve the matrix.  `table` (table_size <= 255 entries)
  * is the codebook every value must match bit for bit (the first equal entry's id);
  * NULL takes the values' distinct bit patterns in CSR order (SM_ERR_NOT_SUPPORTED past
- * 255).  A matrix that already holds the encoding is left as it is.  Not concurrent with
+ * 255).  A matrix sm_create_transpose made from a dense-index one, given that one's codebook,
+ * uses the ids the index gave the terms instead (equal entries stay apart).
+ * A matrix that already holds the encoding is left as it is.  Not concurrent with
  * other calls on the matrix.  Additive: the reference cannot hold a matrix without it. */
 SM_API sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t table_size);
 

@@ -39,7 +39,7 @@ EXPORTS = (
     "sm_version", "sm_status_string", "sm_last_error", "sm_device_count",
     "sm_create_from_dense_index", "sm_create_from_dense_index_device", "sm_create_from_csr",
     "sm_create_from_csr_device", "sm_build_opts_init", "sm_create_from_csr_ex",
-    "sm_create_from_csr_device_ex",
+    "sm_create_from_csr_device_ex", "sm_create_transpose",
     "sm_destroy", "sm_get_info", "sm_get_info_ex", "sm_num_rows", "sm_num_cols", "sm_copy_ref_stream",
     "sm_build_ref_stream",
     "sm_copy_csr", "sm_to_dense", "sm_equal", "sm_spmv", "sm_spmm", "sm_addmatmat",
@@ -141,6 +141,7 @@ def _declare(L):
                                    C.POINTER(_vp)], C.c_int),
         "sm_create_from_csr_device_ex": ([_i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp,
                                           C.POINTER(SmBuildOpts), C.POINTER(_vp)], C.c_int),
+        "sm_create_transpose": ([_vp, C.POINTER(SmBuildOpts), _vp, C.POINTER(_vp)], C.c_int),
         "sm_destroy": ([_vp], None),
         "sm_get_info": ([_vp, C.POINTER(SmInfo)], C.c_int),
         "sm_get_info_ex": ([_vp, C.POINTER(SmInfo), C.c_size_t], C.c_int),

@@ -99,6 +99,8 @@ void free_device(sm_matrix *m) {
     (void)hipFree(m->d_row_ptr);
     (void)hipFree(m->d_col);
     (void)hipFree(m->d_val);
+    (void)hipFree(m->d_term_ids);
+    m->d_term_ids = nullptr;
     (void)hipFree(m->plan.d_tiles);
     (void)hipFree(m->plan.d_merge);
     (void)hipFree(m->plan.d_merge_corner);
@@ -1438,6 +1440,111 @@ sm_status sm_create_from_csr_device(int64_t n_rows, int64_t n_cols, int64_t nnz,
                                         stream, nullptr, out);
 }
 
+// Common tail of the device-CSR constructors: `m` holds its sizes, options and the CSR arrays
+// (alloc_csr) filled on `s`.  Validates them by a kernel, plans, and builds the layouts on the
+// device or the host as the options ask.  Synchronises `s`; the caller frees `m` on failure.
+// `exact_sell`: also the unsegmented sliced ELL where want_exact_sell asks for it (the host
+// constructors' last step).
+static sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell) {
+    const int64_t n_rows = m->n_rows, n_cols = m->n_cols, nnz = m->nnz;
+    sm_status st = SM_OK;
+    int32_t *d_flag = nullptr;
+    hipError_t e = hipMalloc((void **)&d_flag, sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), s);
+    if (e == hipSuccess)
+        e = launch_validate((int32_t)n_rows, (int32_t)n_cols, (int32_t)nnz, m->d_row_ptr,
+                            m->d_col, d_flag, s);
+    int32_t flag = 0;
+    std::vector<int32_t> rp((size_t)n_rows + 1);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(rp.data(), m->d_row_ptr, rp.size() * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_flag);
+    if (e != hipSuccess) return hip_fail(e, "sm_create_from_csr_device");
+    if (flag) return fail(SM_ERR_INVALID_MATRIX, "device CSR failed validation (flags 0x%x)", flag);
+    st = upload_plan(m, rp.data());
+    const bool xband = want_xband(m);
+    // The column relabeling and the sorted sliced ELL on the device (builddev.hip) where they
+    // are all this matrix wants: no band layout, sweep, hot split, windowed sort or exact sliced
+    // ELL, and no column-chunked ELL once the relabeling is decided (its builder runs on the
+    // host).  R-MAT 24: the host path took 5.4 s.
+    bool dev_done = false;
+    const bool dev_ok = st == SM_OK && m->opts.host_build == 0 && !want_sweep(m) && m->opts.hot_cols <= 0 &&
+                        m->opts.sell_sigma == 0 && m->opts.sell_streams <= 1 && m->opts.exact_sell != 1;
+    // The gathered chunk bands on the device (builddev_gcb.hip; config 5: 15 s on the host path).
+    // Declined (a row's columns not ascending, size limits): the host path below decides.
+    // A forced column relabeling (relabel = 1) is built beside the bands by the host path
+    // only, so the device path is declined there too: the same bytes either way.
+    if (dev_ok && xband && xband_kind_setting(m) == kXbGcb && m->opts.relabel != 1) {
+        hipError_t eb = hipSuccess;
+        int rows_log2 = 0;
+        int32_t slabs = 1;
+        gcb_geometry(m, rows_log2, slabs);
+        GcbHost meta;
+        const int rc = devbuild_gcb(m, rows_log2, slabs, kGcbMaxWindow, meta, s, eb);
+        if (rc < 0) st = hip_fail(eb, "device gcb builder");
+        else if (rc == 0) {
+            st = gcb_finish(m, meta);
+            dev_done = st == SM_OK;
+        }
+    }
+    if (dev_ok && !xband) {
+        hipError_t eb = hipSuccess;
+        int rc = 0;
+        if (want_relabel_size(m)) rc = devbuild_relabel(m, m->opts.relabel != 1, s, eb);
+        if (rc == 0 && !want_ccsell(m)) {
+            if (want_sell(m)) {
+                const int32_t max_len = m->opts.sell_max_len > 0 ? m->opts.sell_max_len : kSellMaxLen;
+                rc = devbuild_sell(m, max_len, m->opts.sell_codebook != 0, s, eb);
+            }
+            dev_done = rc == 0;
+        }
+        if (rc != 0) st = hip_fail(eb, "device layout builder");
+    }
+    // The merge path's staging copy (sm_build_opts.merge_stage) after a device build too
+    // (R-MAT 24: 7.7 s on the host path).
+    if (st == SM_OK && dev_done && want_merge_stage(m)) {
+        hipError_t eb = hipSuccess;
+        if (devbuild_merge_stage(m, s, eb) < 0) st = hip_fail(eb, "device merge staging builder");
+    }
+    const bool maybe_sell = m->opts.sell != 0 && nnz > 0;
+    const bool maybe_xsell = exact_sell && nnz > 0 && n_rows > 0 && (m->opts.exact_sell == 1 || (m->opts.exact_sell == 0 && m->from_index));
+    // The band / sell builders run on the host (band2.cpp, xband.cpp, sell.cpp): the
+    // columns come down for any of them, the values only for the layout that stores
+    // them (4 + 4 bytes per term over PCIe once, at creation).
+    if (st == SM_OK && !dev_done &&
+        (xband || want_relabel_size(m) || maybe_sell || maybe_xsell || want_sweep(m) || want_merge_stage(m))) {
+        std::vector<int32_t> ch((size_t)nnz);
+        std::vector<float> vh;
+        auto values = [&]() -> sm_status {
+            if (vh.size() == (size_t)nnz) return SM_OK;
+            vh.resize((size_t)nnz);
+            const hipError_t ev = hipMemcpy(vh.data(), m->d_val, (size_t)nnz * 4, hipMemcpyDeviceToHost);
+            return ev == hipSuccess ? SM_OK : hip_fail(ev, "copy CSR values for the layout builder");
+        };
+        hipError_t e3 = hipSuccess;
+        if (nnz) e3 = hipMemcpy(ch.data(), m->d_col, (size_t)nnz * 4, hipMemcpyDeviceToHost);
+        st = e3 == hipSuccess ? SM_OK : hip_fail(e3, "copy CSR columns for the layout builder");
+        if (st == SM_OK && xband) st = values();
+        if (st == SM_OK && xband) st = upload_xband(m, rp.data(), ch.data(), vh.data(), xband_kind_setting(m));
+        if (st == SM_OK && want_sweep(m)) st = values();
+        if (st == SM_OK && want_sweep(m)) st = upload_sweep(m, rp.data(), ch.data(), vh.data());
+        if (st == SM_OK && want_relabel_size(m)) st = upload_relabel(m, ch.data());
+        if (st == SM_OK && want_ccsell(m)) st = values();
+        if (st == SM_OK && want_ccsell(m)) st = upload_ccsell(m, rp.data(), ch.data(), vh.data());
+        if (st == SM_OK && want_sell(m)) st = values();
+        if (st == SM_OK && want_sell(m)) st = upload_sell_layouts(m, rp.data(), ch.data(), vh.data());
+        if (st == SM_OK && want_merge_stage(m)) st = values();
+        if (st == SM_OK && want_merge_stage(m))
+            st = upload_merge_stage(m, rp.data(), ch.data(), vh.data());
+        if (st == SM_OK && exact_sell && want_exact_sell(m)) st = values();
+        if (st == SM_OK && exact_sell && want_exact_sell(m))
+            st = upload_exact_sell(m, rp.data(), ch.data(), vh.data());
+    }
+    return st;
+}
+
 sm_status sm_create_from_csr_device_ex(int64_t n_rows, int64_t n_cols, int64_t nnz,
                                        const int32_t *d_row_ptr, const int32_t *d_col_idx,
                                        const float *d_val, int32_t device, sm_stream stream,
@@ -1470,103 +1577,108 @@ sm_status sm_create_from_csr_device_ex(int64_t n_rows, int64_t n_cols, int64_t n
         if (e == hipSuccess)
             e = hipMemcpyAsync(m->d_val, d_val, (size_t)nnz * 4, hipMemcpyDeviceToDevice, s);
     }
-    int32_t *d_flag = nullptr;
-    if (e == hipSuccess) e = hipMalloc((void **)&d_flag, sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), s);
-    if (e == hipSuccess)
-        e = launch_validate((int32_t)n_rows, (int32_t)n_cols, (int32_t)nnz, m->d_row_ptr,
-                            m->d_col, d_flag, s);
-    int32_t flag = 0;
-    std::vector<int32_t> rp((size_t)n_rows + 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(rp.data(), m->d_row_ptr, rp.size() * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_flag);
     if (e != hipSuccess) {
         free_device(m.get());
         return hip_fail(e, "sm_create_from_csr_device");
     }
-    if (flag) {
-        free_device(m.get());
-        return fail(SM_ERR_INVALID_MATRIX, "device CSR failed validation (flags 0x%x)", flag);
-    }
-    st = upload_plan(m.get(), rp.data());
-    const bool xband = want_xband(m.get());
-    // The column relabeling and the sorted sliced ELL on the device (builddev.hip) where they
-    // are all this matrix wants: no band layout, sweep, hot split, windowed sort or exact sliced
-    // ELL, and no column-chunked ELL once the relabeling is decided (its builder runs on the
-    // host).  R-MAT 24: the host path took 5.4 s.
-    bool dev_done = false;
-    const bool dev_ok = st == SM_OK && m->opts.host_build == 0 && !want_sweep(m.get()) && m->opts.hot_cols <= 0 &&
-                        m->opts.sell_sigma == 0 && m->opts.sell_streams <= 1 && m->opts.exact_sell != 1;
-    // The gathered chunk bands on the device (builddev_gcb.hip; config 5: 15 s on the host path).
-    // Declined (a row's columns not ascending, size limits): the host path below decides.
-    // A forced column relabeling (relabel = 1) is built beside the bands by the host path
-    // only, so the device path is declined there too: the same bytes either way.
-    if (dev_ok && xband && xband_kind_setting(m.get()) == kXbGcb && m->opts.relabel != 1) {
-        hipError_t eb = hipSuccess;
-        int rows_log2 = 0;
-        int32_t slabs = 1;
-        gcb_geometry(m.get(), rows_log2, slabs);
-        GcbHost meta;
-        const int rc = devbuild_gcb(m.get(), rows_log2, slabs, kGcbMaxWindow, meta, s, eb);
-        if (rc < 0) st = hip_fail(eb, "device gcb builder");
-        else if (rc == 0) {
-            st = gcb_finish(m.get(), meta);
-            dev_done = st == SM_OK;
-        }
-    }
-    if (dev_ok && !xband) {
-        hipError_t eb = hipSuccess;
-        int rc = 0;
-        if (want_relabel_size(m.get())) rc = devbuild_relabel(m.get(), m->opts.relabel != 1, s, eb);
-        if (rc == 0 && !want_ccsell(m.get())) {
-            if (want_sell(m.get())) {
-                const int32_t max_len = m->opts.sell_max_len > 0 ? m->opts.sell_max_len : kSellMaxLen;
-                rc = devbuild_sell(m.get(), max_len, m->opts.sell_codebook != 0, s, eb);
-            }
-            dev_done = rc == 0;
-        }
-        if (rc != 0) st = hip_fail(eb, "device layout builder");
-    }
-    // The merge path's staging copy (sm_build_opts.merge_stage) after a device build too
-    // (R-MAT 24: 7.7 s on the host path).
-    if (st == SM_OK && dev_done && want_merge_stage(m.get())) {
-        hipError_t eb = hipSuccess;
-        if (devbuild_merge_stage(m.get(), s, eb) < 0) st = hip_fail(eb, "device merge staging builder");
-    }
-    const bool maybe_sell = m->opts.sell != 0 && nnz > 0;
-    // The band / sell builders run on the host (band2.cpp, xband.cpp, sell.cpp): the
-    // columns come down for any of them, the values only for the layout that stores
-    // them (4 + 4 bytes per term over PCIe once, at creation).
-    if (st == SM_OK && !dev_done &&
-        (xband || want_relabel_size(m.get()) || maybe_sell || want_sweep(m.get()) || want_merge_stage(m.get()))) {
-        std::vector<int32_t> ch((size_t)nnz);
-        std::vector<float> vh;
-        auto values = [&]() -> sm_status {
-            if (vh.size() == (size_t)nnz) return SM_OK;
-            vh.resize((size_t)nnz);
-            const hipError_t ev = hipMemcpy(vh.data(), m->d_val, (size_t)nnz * 4, hipMemcpyDeviceToHost);
-            return ev == hipSuccess ? SM_OK : hip_fail(ev, "copy CSR values for the layout builder");
-        };
-        hipError_t e3 = hipSuccess;
-        if (nnz) e3 = hipMemcpy(ch.data(), m->d_col, (size_t)nnz * 4, hipMemcpyDeviceToHost);
-        st = e3 == hipSuccess ? SM_OK : hip_fail(e3, "copy CSR columns for the layout builder");
-        if (st == SM_OK && xband) st = values();
-        if (st == SM_OK && xband) st = upload_xband(m.get(), rp.data(), ch.data(), vh.data(), xband_kind_setting(m.get()));
-        if (st == SM_OK && want_sweep(m.get())) st = values();
-        if (st == SM_OK && want_sweep(m.get())) st = upload_sweep(m.get(), rp.data(), ch.data(), vh.data());
-        if (st == SM_OK && want_relabel_size(m.get())) st = upload_relabel(m.get(), ch.data());
-        if (st == SM_OK && want_ccsell(m.get())) st = values();
-        if (st == SM_OK && want_ccsell(m.get())) st = upload_ccsell(m.get(), rp.data(), ch.data(), vh.data());
-        if (st == SM_OK && want_sell(m.get())) st = values();
-        if (st == SM_OK && want_sell(m.get())) st = upload_sell_layouts(m.get(), rp.data(), ch.data(), vh.data());
-        if (st == SM_OK && want_merge_stage(m.get())) st = values();
-        if (st == SM_OK && want_merge_stage(m.get()))
-            st = upload_merge_stage(m.get(), rp.data(), ch.data(), vh.data());
-    }
+    st = finish_from_device_csr(m.get(), s, false);
     if (st != SM_OK) { free_device(m.get()); return st; }
+    *out = m.release();
+    return SM_OK;
+}
+
+// The codebook ids of a CopyForm-built matrix's terms in CSR order, on the device: read back
+// from the reference stream it holds (encode.cpp: per panel of 256 B rows the entries run by
+// B column, then B row -- every B row's entries in its CSR order; (255, T) entries are
+// fillers).  *d_ids stays null when the matrix holds no stream (nothing to hand on).
+static sm_status ids_from_ref_stream(const sm_matrix *src, uint8_t **d_ids) {
+    *d_ids = nullptr;
+    if (!src->has_ref || src->nnz == 0 || src->table_size <= 0) return SM_OK;
+    std::vector<int32_t> fill((size_t)src->n_rows + 1);
+    SM_TRY_HIP(hipMemcpy(fill.data(), src->d_row_ptr, fill.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint8_t> ids((size_t)src->nnz);
+    const uint8_t T = (uint8_t)src->table_size;
+    int64_t seen = 0;
+    for (size_t p = 0; p < src->panel_col_off.size(); p++) {
+        const int64_t row0 = src->panel_col_off[p];
+        int64_t lin = 0;
+        for (int64_t i = src->panel_begin[p]; i < src->panel_end[p]; i++) {
+            lin += src->pos[(size_t)i];
+            const uint8_t id = src->val[(size_t)i];
+            if (id >= T) continue;   // filler step
+            const int64_t row = row0 + (lin & 255);
+            if (row >= src->n_rows || fill[(size_t)row] >= src->nnz) return fail(SM_ERR_INVALID_MATRIX, "reference stream and CSR disagree");
+            ids[(size_t)fill[(size_t)row]++] = id;
+            seen++;
+        }
+    }
+    if (seen != src->nnz) return fail(SM_ERR_INVALID_MATRIX, "reference stream and CSR disagree");
+    int64_t scratch = 0;
+    SM_TRY_HIP(dev_alloc(d_ids, src->nnz, scratch));
+    const hipError_t e = hipMemcpy(*d_ids, ids.data(), ids.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(*d_ids);
+        *d_ids = nullptr;
+        return hip_fail(e, "upload term ids");
+    }
+    return SM_OK;
+}
+
+// B^T of a held matrix: its device CSR transposed on the device (transpose_dev.hip) straight
+// into the new matrix's arrays, then the device-CSR constructors' tail.  A CopyForm-built source
+// hands on its codebook and its default options, so the result is the twin CopyForm would build
+// from the same index with the other `trans` (but for the reference stream, which
+// sm_build_ref_stream adds).
+sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts, sm_stream stream,
+                              sm_matrix **out) {
+    if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (!src) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    sm_status st = check_opts(opts);
+    if (st != SM_OK) return st;
+    st = check_sizes(src->n_cols, src->n_rows, src->nnz);
+    if (st != SM_OK) return st;
+    DeviceGuard g(src->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    auto m = new_matrix(src->device, opts);
+    m->n_rows = src->n_cols;
+    m->n_cols = src->n_rows;
+    m->nnz = src->nnz;
+    m->s_rows = src->s_cols;
+    m->s_cols = src->s_rows;
+    if (src->from_index) {   // the CopyForm path: SM_ALGO_EXACT keeps a reference-order kernel
+        m->from_index = true;
+        m->table_size = src->table_size;
+        m->table = src->table;
+        if (m->opts.exact_sell == 0) m->opts.exact_sell = 1;
+    }
+    st = alloc_csr(m.get());
+    if (st == SM_OK) {
+        const hipError_t e = transpose_csr_device(src->d_row_ptr, src->d_col, src->d_val, src->n_rows, src->n_cols,
+                                                  src->nnz, m->d_row_ptr, m->d_col, m->d_val, s);
+        if (e != hipSuccess) st = hip_fail(e, "sm_create_transpose");
+    }
+    if (st == SM_OK && src->from_index && src->nnz > 0) {
+        // The ids travel too (1 byte per term): the codebook alone cannot tell equal entries apart.
+        uint8_t *own = nullptr;
+        if (!src->d_term_ids) st = ids_from_ref_stream(src, &own);
+        const uint8_t *ids = src->d_term_ids ? src->d_term_ids : own;
+        if (st == SM_OK && ids) {
+            hipError_t e = dev_alloc(&m->d_term_ids, m->nnz, m->device_bytes);
+            if (e == hipSuccess)
+                e = transpose_ids_device(src->d_row_ptr, src->d_col, ids, src->n_rows, src->n_cols, src->nnz,
+                                         m->d_term_ids, s);
+            if (e != hipSuccess) st = hip_fail(e, "sm_create_transpose (term ids)");
+        }
+        (void)hipFree(own);
+    }
+    if (st == SM_OK) st = finish_from_device_csr(m.get(), s, true);
+    if (st != SM_OK) {
+        free_device(m.get());
+        (void)hipGetLastError();   // a failed allocation leaves no sticky error behind
+        return st;
+    }
     *out = m.release();
     return SM_OK;
 }
@@ -1732,13 +1844,25 @@ sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t table_si
     // copy (sm_copy_ref_stream, sm_equal) and derives the native layout's batch metadata.
     EncodeResult er;
     hipError_t he = hipSuccess;
-    const int rc = encode_csr_ref_device(m->d_row_ptr, m->d_col, m->d_val, nullptr, m->n_rows, m->n_cols,
+    // A transposed CopyForm matrix given its own codebook: the ids the index gave its terms.
+    const uint8_t *ids = nullptr;
+    if (m->d_term_ids && table && table_size > 0 && table_size == m->table_size &&
+        m->table.size() >= (size_t)table_size && memcmp(table, m->table.data(), (size_t)table_size * 4) == 0)
+        ids = m->d_term_ids;
+    const int rc = encode_csr_ref_device(m->d_row_ptr, m->d_col, m->d_val, ids, m->n_rows, m->n_cols,
                                          m->nnz, table, table_size, er, nullptr, he);
     if (rc == -5) return hip_fail(he, "sm_build_ref_stream");
     if (rc == -2) return fail(SM_ERR_INVALID_ARG, "a value is not in the codebook");
     if (rc == -3) return fail(SM_ERR_NOT_SUPPORTED, "more than 255 distinct values: no uint8 ids");
     if (rc == -4) return fail(SM_ERR_NOT_SUPPORTED, "S rows >= 2^23: the reference's int32 offsets overflow");
     if (rc != 0) return fail(SM_ERR_INVALID_ARG, "bad codebook");
+    // d_term_ids indexes m->table and lives only while no stream is held: from here the stream
+    // carries the ids (of whichever codebook was given), so the carried ones go.
+    if (m->d_term_ids) {
+        (void)hipFree(m->d_term_ids);
+        m->d_term_ids = nullptr;
+        m->device_bytes -= std::max<int64_t>(m->nnz, 1);
+    }
     m->table_size = er.table_size;
     m->table = std::move(er.table);
     m->pos = std::move(er.pos);

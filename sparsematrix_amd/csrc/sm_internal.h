@@ -315,6 +315,17 @@ int devbuild_merge_stage(sm_matrix *m, hipStream_t s, hipError_t &err);
 struct GcbHost;
 int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, GcbHost &meta, hipStream_t s,
                  hipError_t &err);
+// The CSR of B^T (transpose_dev.hip) from the device CSR of B (n_rows x n_cols, validated): row c
+// holds column c's terms by ascending source row, equal rows in stored order; values bit for
+// bit.  t_rp: n_cols + 1, t_col / t_val: nnz, on the same device.  Synchronises `s`; frees its
+// scratch and leaves no sticky HIP error on failure.
+hipError_t transpose_csr_device(const int32_t *rp, const int32_t *col, const float *val, int64_t n_rows,
+                                int64_t n_cols, int64_t nnz, int32_t *t_rp, int32_t *t_col, float *t_val,
+                                hipStream_t s);
+// The terms' codebook ids (one byte per term, CSR order, on the device) in the order the
+// transposition above gives the terms.
+hipError_t transpose_ids_device(const int32_t *rp, const int32_t *col, const uint8_t *ids, int64_t n_rows,
+                                int64_t n_cols, int64_t nnz, uint8_t *t_ids, hipStream_t s);
 hipError_t launch_validate(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t *rp,
                            const int32_t *col, int32_t *d_flag, hipStream_t s);
 // Dense decode: out is zeroed by the caller.  b_layout: out[row*stride+col]
@@ -347,6 +358,12 @@ struct sm_matrix {
     bool from_index = false;   // built by the CopyForm constructors (the reference's path)
     int32_t table_size = 0;
     std::vector<float> table;                  // table_size + 1, last = 0
+    // The terms' ids into `table` (nnz bytes, CSR order), only on a matrix sm_create_transpose
+    // made from a CopyForm-built one: equal codebook entries keep the ids the index gave them,
+    // so sm_build_ref_stream with that codebook yields the reference's own stream.  Invariant:
+    // they index `table` and exist only while has_ref is false (sm_build_ref_stream frees them:
+    // the stream then holds the ids, and sm_create_transpose reads them back from it).
+    uint8_t *d_term_ids = nullptr;
     std::vector<uint8_t> pos, val;
     std::vector<int32_t> panel_row_off, panel_col_off;
     std::vector<int64_t> panel_begin, panel_end;

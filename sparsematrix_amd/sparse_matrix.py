@@ -38,6 +38,8 @@ def _is_device(a) -> bool:
 
 
 def _stream_of(t, stream) -> int:
+    """`stream` as a raw handle; None: the current torch stream of t.device (a tensor's, or a
+    SparseMatrix's device ordinal)."""
     if stream is not None:
         return int(stream) if isinstance(stream, int) else int(stream.cuda_stream)
     import torch
@@ -78,6 +80,7 @@ class SparseMatrix:
                  vals=None, val_table_size: int = 0, trans: int = SblasNoTrans,
                  device: int = 0):
         self._h = None
+        self._t = None   # the cached transposed companion (T)
         self.device = device
         self._L = _lib.load()
         if density_matrix is not None:
@@ -85,7 +88,10 @@ class SparseMatrix:
 
     # ---- lifetime ---------------------------------------------------------
     def Destroy(self) -> None:
-        """sparse-matrix.cc:9-18."""
+        """sparse-matrix.cc:9-18.  Also releases the cached transposed companion (T)."""
+        t, self._t = getattr(self, "_t", None), None
+        if t is not None:
+            t.Destroy()
         if self._h:
             self._L.sm_destroy(self._h)
         self._h = None
@@ -185,6 +191,44 @@ class SparseMatrix:
         self._h = h
         return self
 
+    # ---- the transposed matrix ---------------------------------------------
+    def transposed(self, opts: Optional[dict] = None, stream=None) -> "SparseMatrix":
+        """A new, independent SparseMatrix holding B^T (sm_create_transpose): transposed on the
+        device from this matrix's device CSR -- row c of B^T holds column c's terms by ascending
+        source row, values bit for bit.  `opts`: the fields of sm_build_opts, as for from_csr
+        (None: the constructors' defaults).  A CopyForm-built matrix gives what CopyForm builds
+        from the same index with the other `trans` (without the reference stream:
+        build_ref_stream adds it).  Synchronises `stream` (None: the current torch stream)."""
+        h0 = self._require()
+        t = SparseMatrix(device=self.device)
+        o = _lib.build_opts(**(opts or {}))
+        h = C.c_void_p()
+        st = self._L.sm_create_transpose(h0, C.byref(o), _stream_of(self, stream), C.byref(h))
+        check(st, "transposed")
+        t._h = h
+        return t
+
+    @property
+    def T(self) -> "SparseMatrix":
+        """The transposed companion, built on first use (transposed() with default options)
+        and cached until CopyForm or Destroy.  It is a second matrix on the device: holding it
+        doubles the device memory held.  ``m.T.T`` is a third matrix equal to ``m`` (``==``),
+        not ``m`` itself."""
+        self._require()
+        if self._t is None:
+            self._t = self.transposed()
+        return self._t
+
+    def spmv_t(self, x, y, alpha: float = 1.0, beta: float = 1.0, algo="auto", stream=None):
+        """y = alpha * B^T * x + beta * y on device tensors: spmv on the cached companion T
+        (x: n_rows elements, y: n_cols elements of this matrix)."""
+        return self.T.spmv(x, y, alpha, beta, algo, stream)
+
+    def spmm_t(self, X, Y, alpha: float = 1.0, beta: float = 1.0, algo="auto", stream=None):
+        """Y (k x N) = alpha * B^T * X (n x N) + beta * Y, row-major device tensors: spmm on
+        the cached companion T."""
+        return self.T.spmm(X, Y, alpha, beta, algo, stream)
+
     # ---- queries ----------------------------------------------------------
     def NumRows(self) -> int:
         """rows_ = k of the S view (sparse-matrix.h:39)."""
@@ -231,7 +275,9 @@ class SparseMatrix:
         """Encode a CSR-built matrix in the reference's format (sm_build_ref_stream,
         sparse-matrix.cc:20-99): afterwards ref_stream(), == and algo="native" serve it.
         `table`: the codebook (<= 255 fp32 values every value must match); None takes the
-        values' distinct bit patterns in CSR order."""
+        values' distinct bit patterns in CSR order.  On the transposed() of a CopyForm-built
+        matrix, that matrix's own codebook gives the stream CopyForm builds with the other
+        `trans` (the terms keep the ids the index gave them)."""
         if table is None:
             check(self._L.sm_build_ref_stream(self._h, None, 0), "sm_build_ref_stream")
             return
