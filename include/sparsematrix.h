@@ -349,6 +349,13 @@ SM_API sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t t
 /* Host copy of the device CSR (row_ptr n_rows+1, col_idx/val nnz). */
 SM_API sm_status sm_copy_csr(const sm_matrix *m, int32_t *row_ptr, int32_t *col_idx, float *val);
 
+/* Device copy of the device CSR (row_ptr n_rows+1, col_idx / val nnz) into buffers on the
+ * matrix's device, asynchronous on `stream`; any of the three pointers may be NULL to skip that
+ * array.  With sm_create_from_csr_device it rebuilds a matrix from updated values without a
+ * host round trip. */
+SM_API sm_status sm_copy_csr_device(const sm_matrix *m, int32_t *d_row_ptr, int32_t *d_col_idx,
+                                    float *d_val, sm_stream stream);
+
 /* CopyTo (sparse-matrix.cc:101-137), host output.  NoTrans writes S
  * (s_rows x stride), Trans writes S^T (s_cols x stride); untouched elements
  * are zeroed.  Decoded on the device. */
@@ -367,6 +374,48 @@ SM_API sm_status sm_spmv(const sm_matrix *m, float alpha, const float *x, float 
 SM_API sm_status sm_spmm(const sm_matrix *m, int32_t n_rhs, float alpha, const float *X,
                          int64_t ldx, float beta, float *Y, int64_t ldy, sm_algo algo,
                          sm_stream stream);
+
+/* Sampled dense-dense product over the matrix's own pattern (SDDMM), no reference equivalent:
+ *   out[e] = alpha * sum_j G[r_e*ldg + j] * X[c_e*ldx + j] + beta * out[e],   0 <= j < n_rhs,
+ * for every stored term e = (r_e, c_e) of B in CSR order (the order sm_copy_csr returns).  With
+ * G = dL/dY it is dL/dval of Y = alpha * B * X: the gradient of the stored values.
+ * Operands: G is n_rows x n_rhs and X is n_cols x n_rhs, both row-major with ldg, ldx >= n_rhs;
+ *   `out` has nnz floats and must not overlap G or X.  n_rhs >= 1 (else SM_ERR_INVALID_ARG);
+ *   n_rhs = 1 is the SpMV case g[r] * x[c].
+ * Terms: the stored entries of the B = S^T CSR, explicit zeros included, whatever constructor
+ *   made the matrix.  nnz = 0 returns SM_OK and launches nothing.
+ * Placement: any 4-byte aligned G, X, out and any ld is correct; placement only selects the
+ *   kernel.  The vector kernel takes 16-byte aligned G and X with ldg % 4 == 0, ldx % 4 == 0
+ *   (and n_rhs % 4 == 0, G and X each under 4 GiB); the one-lane-per-term kernel takes everything
+ *   else.  Nothing outside out[0, nnz) is written; G and X are never written; row offsets are
+ *   formed in 64 bits.
+ * beta, alpha: as everywhere in the library.  `out` is multiplied by beta whenever beta != 1 (so
+ *   beta = 0 propagates NaN/Inf already in `out`) and added unscaled when beta == 1.  alpha == 0
+ *   skips the product: G and X are not read and may be NULL, only the beta scaling runs.
+ * SM_ALGO_PARITY: one order, every operation rounded separately (no fused multiply-add):
+ *     s = fl(G[r,0] * X[c,0]);   s = fl(s + fl(G[r,j] * X[c,j]))  for j = 1 .. n_rhs-1;
+ *     t = fl(alpha * s);   out = fl(out + t) if beta == 1, else fl(fl(beta * out) + t)
+ *   -- bit-identical to that restatement for every term (n_rhs + 2 roundings on the longest path).
+ * SM_ALGO_AUTO (every other sm_algo value runs as AUTO: the SpMV layouts do not matter here):
+ *   deterministic -- the same inputs give the same bits on every run; no float atomics, and the
+ *   launch geometry is a function of n_rhs alone.  n_rhs <= 3, or a placement the vector kernel
+ *   does not take: the PARITY kernel, bit-identical to PARITY (so n_rhs = 1 always is).
+ *   Otherwise the vector kernel: L = min(64, the power of two >= n_rhs / 4) lanes share a term,
+ *   lane g owns the elements [4g, 4g+4) + 4L*t, t = 0 .. T-1, T = ceil(n_rhs / 4L); its partial is
+ *   one fused multiply-add per element in ascending j (4T roundings), the L partials are added in
+ *   a fixed xor tree, lane distances L/2 ... 1 (log2 L roundings), then t = fl(alpha * s) and the
+ *   add onto beta * out as above: 4T + log2 L + 2 roundings on the longest path -- 6 at n_rhs = 4,
+ *   9 at 32, 12 at 256, 16 at 512.  Every result is within
+ *     |out - exact| <= 1e-6 * (|alpha| * sum_j |G*X| + |beta * out_0|)
+ *   in the worst case while that count is <= 16 (16 * 2^-24 < 1e-6), i.e. for the vector kernel up
+ *   to n_rhs = 512 and for the one-lane-per-term kernel up to n_rhs = 14; past that the bound
+ *   holds for all but adversarial data (errors of random sign grow with the square root).
+ * Streams: asynchronous on `stream`; no allocation, no host synchronisation and no matrix scratch,
+ *   so the call can be captured in a HIP graph, and calls on one matrix from several streams need
+ *   no ordering (the matrix is only read). */
+SM_API sm_status sm_sddmm(const sm_matrix *m, int32_t n_rhs, float alpha, const float *G, int64_t ldg,
+                          const float *X, int64_t ldx, float beta, float *out, sm_algo algo,
+                          sm_stream stream);
 
 /* AddMatMat (sparse-matrix.cc:139-194) on device pointers:
  * C (m x n, ldc) = alpha * A (m x k, lda) * S + beta * C.

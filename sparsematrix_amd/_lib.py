@@ -47,7 +47,7 @@ EXPORTS = (
     "sm_multi_last_error", "sm_multi_partition", "sm_multi_unique_id", "sm_multi_create",
     "sm_multi_destroy", "sm_multi_spmv", "sm_multi_spmm", "sm_multi_spmv_batch",
     "sm_multi_allgather", "sm_multi_set_timing", "sm_multi_last_times", "sm_multi_create_with",
-    "sm_debug_seed_handoff", "sm_layout_digest",
+    "sm_debug_seed_handoff", "sm_layout_digest", "sm_sddmm", "sm_copy_csr_device",
 )
 
 SM_UNIQUE_ID_BYTES = 128
@@ -155,6 +155,8 @@ def _declare(L):
         "sm_equal": ([_vp, _vp], _i32),
         "sm_spmv": ([_vp, _f32, _vp, _f32, _vp, C.c_int, _vp], C.c_int),
         "sm_spmm": ([_vp, _i32, _f32, _vp, _i64, _f32, _vp, _i64, C.c_int, _vp], C.c_int),
+        "sm_sddmm": ([_vp, _i32, _f32, _vp, _i64, _vp, _i64, _f32, _vp, C.c_int, _vp], C.c_int),
+        "sm_copy_csr_device": ([_vp, _vp, _vp, _vp, _vp], C.c_int),
         "sm_addmatmat": ([_vp, _vp, _i32, _i32, _vp, _i32, _f32, _f32, C.c_int, _vp], C.c_int),
         "sm_addmatmat_host": ([_vp, _vp, _i32, _i32, _vp, _i32, _f32, _f32], C.c_int),
         "sm_beta_scale": ([_vp, _i32, _i32, _i32, _f32, _vp], C.c_int),

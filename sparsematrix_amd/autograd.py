@@ -2,12 +2,18 @@
 
 Plumbing only: the forward pass is the matrix's own ``spmv`` / ``spmm`` into a zeroed
 output (beta = 0), the backward pass the same product on the cached transposed companion
-``matrix.T`` (``grad_X = alpha * B^T * grad_Y``).  All arithmetic stays in the library's HIP
-kernels; the matrix itself gets no gradient.
+``matrix.T`` (``grad_X = alpha * B^T * grad_Y``) and, for the stored values, the matrix's
+``sddmm`` (``grad_values[e] = alpha * <grad_Y[r_e, :], X[c_e, :]>`` in CSR order).  All
+arithmetic stays in the library's HIP kernels.
 
     from sparsematrix_amd import autograd
     Y = autograd.apply(m, X, alpha=1.3)     # X: n_cols (SpMV) or n_cols x N row-major (SpMM)
     Y.backward(G)                            # X.grad = 1.3 * m.T @ G
+
+    rp, ci, val = m.csr_device()             # the stored values as a leaf
+    val.requires_grad_()
+    Y = autograd.apply(m, X, alpha=1.3, values=val)
+    Y.backward(G)                            # val.grad = m.sddmm(G, X, alpha=1.3)
 """
 from __future__ import annotations
 
@@ -36,25 +42,53 @@ def _function():
 
     class SparseMatMul(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, X, matrix, alpha):
+        def forward(ctx, X, matrix, alpha, values):
             ctx.matrix, ctx.alpha = matrix, float(alpha)
-            return _product(matrix, X.detach().contiguous(), ctx.alpha)
+            Xc = X.detach().contiguous()
+            if values is not None and ctx.needs_input_grad[3]:
+                ctx.values_shape = values.shape
+                ctx.save_for_backward(Xc)   # X is kept only when the values want a gradient
+            return _product(matrix, Xc, ctx.alpha)
 
         @staticmethod
         @once_differentiable   # first-order only: a double backward raises instead of going wrong
         def backward(ctx, grad_Y):
-            grad_X = None
+            grad_X = grad_values = None
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[3]:
+                grad_Y = grad_Y.contiguous()
             if ctx.needs_input_grad[0]:
-                grad_X = _product(ctx.matrix.T, grad_Y.contiguous(), ctx.alpha)
-            return grad_X, None, None
+                grad_X = _product(ctx.matrix.T, grad_Y, ctx.alpha)
+            if ctx.needs_input_grad[3]:
+                (Xc,) = ctx.saved_tensors
+                grad_values = ctx.matrix.sddmm(grad_Y, Xc, alpha=ctx.alpha).view(ctx.values_shape)
+            return grad_X, None, None, grad_values
 
     _fn = SparseMatMul
     return _fn
 
 
-def apply(matrix, X, alpha: float = 1.0):
+def apply(matrix, X, alpha: float = 1.0, values=None):
     """Y = alpha * B * X for the SparseMatrix `matrix` (B, n_rows x n_cols) and a float32 device
     tensor X of n_cols elements (1-D) or n_cols x N (row-major; made contiguous if it is not).
     Differentiable in X: backward computes alpha * B^T * grad_Y on ``matrix.T``, which is built
-    on first use and doubles the device memory the matrix holds."""
-    return _function().apply(X, matrix, alpha)
+    on first use and doubles the device memory the matrix holds.
+
+    `values` (optional): a float32 tensor of nnz elements on X's device that stands for the
+    matrix's stored values, in CSR order, as the autograd leaf.  It must hold the values the
+    matrix was built from (``matrix.csr_device()[2]``): the forward pass runs on the held matrix
+    and never reads the tensor.  When it requires a gradient, backward returns
+    ``matrix.sddmm(grad_Y, X, alpha=alpha)`` for it (X is saved for backward only then), and
+    ``matrix.T`` is not built unless X requires a gradient too.  To step the values, rebuild:
+    ``SparseMatrix.from_csr(row_ptr, col_idx, new_values, n_cols)``."""
+    if values is not None:
+        import torch
+        if not isinstance(values, torch.Tensor) or not values.is_cuda:
+            raise TypeError("values must be a CUDA (HIP) torch tensor")
+        if values.dtype != torch.float32:
+            raise TypeError("values must be float32")
+        if values.device != X.device:
+            raise ValueError("values must be on X's device")
+        nnz = matrix._nnz()
+        if values.numel() != nnz:
+            raise ValueError(f"values has {values.numel()} elements, the matrix stores {nnz} terms")
+    return _function().apply(X, matrix, alpha, values)

@@ -2126,6 +2126,48 @@ sm_status sm_spmm(const sm_matrix *m, int32_t n_rhs, float alpha, const float *X
     return e == hipSuccess ? SM_OK : hip_fail(e, "sm_spmm launch");
 }
 
+sm_status sm_sddmm(const sm_matrix *m, int32_t n_rhs, float alpha, const float *G, int64_t ldg,
+                   const float *X, int64_t ldx, float beta, float *out, sm_algo algo, sm_stream stream) {
+    if (n_rhs < 1) return fail(SM_ERR_INVALID_ARG, "n_rhs < 1");   // before the matrix is looked at
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (ldg < n_rhs || ldx < n_rhs) return fail(SM_ERR_INVALID_ARG, "ldg/ldx < n_rhs");
+    if (algo < SM_ALGO_AUTO || algo > SM_ALGO_MERGE) return fail(SM_ERR_INVALID_ARG, "unknown algo %d", (int)algo);
+    if (m->nnz == 0) return SM_OK;
+    if (!out || (alpha != 0.0f && (!G || !X))) return fail(SM_ERR_INVALID_ARG, "null G/X/out");
+    DeviceGuard g(m->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t nnz = (int32_t)m->nnz;
+    hipError_t e;
+    if (alpha == 0.0f) {
+        e = beta != 1.0f ? launch_beta(out, 1, nnz, nnz, beta, s) : hipSuccess;
+        return e == hipSuccess ? SM_OK : hip_fail(e, "sm_sddmm beta");
+    }
+    // Every algo but PARITY is AUTO (the SpMV layouts do not matter here).  n_rhs <= 3 runs the
+    // one-lane-per-term kernel: nothing to share between lanes, and n_rhs = 1 stays bit-identical.
+    if (algo != SM_ALGO_PARITY && sddmm_panel_ok(m->n_rows, m->n_cols, n_rhs, G, ldg, X, ldx))
+        e = launch_sddmm_panel((int32_t)m->n_rows, (int32_t)m->n_cols, nnz, n_rhs, m->d_row_ptr, m->d_col, G, ldg,
+                               X, ldx, out, alpha, beta, s);
+    else
+        e = launch_sddmm_term((int32_t)m->n_rows, nnz, n_rhs, m->d_row_ptr, m->d_col, G, ldg, X, ldx, out, alpha,
+                              beta, s);
+    e = after_launch(e, s, "sm_sddmm");
+    return e == hipSuccess ? SM_OK : hip_fail(e, "sm_sddmm launch");
+}
+
+sm_status sm_copy_csr_device(const sm_matrix *m, int32_t *d_row_ptr, int32_t *d_col_idx, float *d_val,
+                             sm_stream stream) {
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    DeviceGuard g(m->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (d_row_ptr)
+        SM_TRY_HIP(hipMemcpyAsync(d_row_ptr, m->d_row_ptr, (size_t)(m->n_rows + 1) * 4, hipMemcpyDeviceToDevice, s));
+    if (d_col_idx && m->nnz)
+        SM_TRY_HIP(hipMemcpyAsync(d_col_idx, m->d_col, (size_t)m->nnz * 4, hipMemcpyDeviceToDevice, s));
+    if (d_val && m->nnz)
+        SM_TRY_HIP(hipMemcpyAsync(d_val, m->d_val, (size_t)m->nnz * 4, hipMemcpyDeviceToDevice, s));
+    return SM_OK;
+}
+
 sm_status sm_addmatmat(const sm_matrix *mat, const float *a, int32_t m, int32_t lda, float *c,
                        int32_t ldc, float alpha, float beta, sm_algo algo, sm_stream stream) {
     if (!mat) return fail(SM_ERR_INVALID_ARG, "null matrix");

@@ -281,6 +281,20 @@ hipError_t launch_spmm_rowpanel(int32_t n, int32_t nrhs, const int32_t *rp, cons
                                 const float *val, int32_t nnz, const float *X, int64_t ldx,
                                 int64_t x_rows, float *Y, int64_t ldy, float alpha, float beta,
                                 bool allow_pipelined, hipStream_t s);
+// SDDMM (kernels_sddmm.hip): out[e] = alpha * <G[row_e, :], X[col_e, :]> + beta * out[e] for every
+// stored term e in CSR order.  launch_sddmm_term: one lane per term, the SM_ALGO_PARITY order, any
+// placement.  launch_sddmm_panel: lanes share a term's dot; only where sddmm_panel_ok holds
+// (n_rhs % 4 == 0, ld % 4 == 0, G and X 16-byte aligned and under 4 GiB).  Workgroups of the
+// panel kernel take kSddmmChunk consecutive terms each.
+constexpr int kSddmmChunk = 2048;
+hipError_t launch_sddmm_term(int32_t n_rows, int32_t nnz, int32_t n_rhs, const int32_t *rp, const int32_t *col,
+                             const float *G, int64_t ldg, const float *X, int64_t ldx, float *out, float alpha,
+                             float beta, hipStream_t s);
+bool sddmm_panel_ok(int64_t n_rows, int64_t n_cols, int32_t n_rhs, const float *G, int64_t ldg, const float *X,
+                    int64_t ldx);
+hipError_t launch_sddmm_panel(int32_t n_rows, int32_t n_cols, int32_t nnz, int32_t n_rhs, const int32_t *rp,
+                              const int32_t *col, const float *G, int64_t ldg, const float *X, int64_t ldx,
+                              float *out, float alpha, float beta, hipStream_t s);
 hipError_t launch_beta(float *c, int32_t m, int32_t n, int64_t ldc, float beta, hipStream_t s);
 hipError_t launch_transpose(const float *a, int32_t m, int32_t n, int64_t lda, float *sa,
                             int64_t ldsa, hipStream_t s);

@@ -64,6 +64,25 @@ def _check_dev_2d(t, rows: int, cols: int, name: str) -> None:
         raise ValueError(f"{name} must be a row-major {rows} x {cols} (or larger) view")
 
 
+def _sddmm_operand(t, rows: int, name: str):
+    """(n_rhs, ld) of an sddmm operand: `rows` elements (1-D, unit stride: n_rhs = 1) or a
+    row-major rows x n_rhs view (stride(1) == 1, stride(0) >= n_rhs)."""
+    _check_dev(t, 0, name)
+    if t.dim() == 1:
+        if t.shape[0] != rows or (rows > 1 and t.stride(0) != 1):
+            raise ValueError(f"{name} must be a unit-stride 1-D tensor of {rows} elements")
+        return 1, 1
+    if t.dim() != 2 or t.shape[0] != rows:
+        raise ValueError(f"{name} must have {rows} elements (1-D) or {rows} rows (2-D), got {tuple(t.shape)}")
+    n = int(t.shape[1])
+    if n > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name} must be row-major (stride(1) == 1)")
+    ld = int(t.stride(0)) if rows > 1 else n
+    if ld < n:
+        raise ValueError(f"{name} has stride(0) = {ld} < {n} columns")
+    return n, ld
+
+
 def _algo(algo) -> int:
     if isinstance(algo, int):
         return algo
@@ -376,6 +395,63 @@ class SparseMatrix:
                              _ptr(Y), int(Y.stride(0)), _algo(algo), _stream_of(Y, stream))
         check(st, "sm_spmm")
         return Y
+
+    def sddmm(self, G, X, out=None, alpha: float = 1.0, beta: float = 0.0, algo="auto",
+              stream=None):
+        """out[e] = alpha * <G[r_e, :], X[c_e, :]> + beta * out[e] for every stored term e of B
+        in CSR order (sm_sddmm): with G = dL/dY, the gradient of the stored values of
+        Y = alpha * B * X.  G (n_rows x N) and X (n_cols x N) are float32 device tensors, row-major
+        with stride(1) == 1 and any stride(0) >= N; 1-D G and X of n_rows / n_cols elements mean
+        N = 1.  `out`: nnz float32 elements, contiguous; None allocates zeros (beta scales what
+        is there, so uninitialised memory will not do).  Returns `out`."""
+        import torch
+        n_rows, n_cols = self._dims()
+        h = self._require()
+        nnz = self._nnz()
+        n_rhs, ldg = _sddmm_operand(G, n_rows, "G")
+        n_x, ldx = _sddmm_operand(X, n_cols, "X")
+        if n_x != n_rhs:
+            raise ValueError(f"G has {n_rhs} columns, X has {n_x}")
+        if n_rhs < 1:
+            raise ValueError("G and X need at least one column")
+        if G.device != X.device:
+            raise ValueError("G and X must be on the same device")
+        if out is None:
+            out = torch.zeros(nnz, dtype=torch.float32, device=G.device)
+        else:
+            _check_dev(out, nnz, "out")
+            if out.dim() != 1 or out.numel() != nnz or (nnz > 1 and out.stride(0) != 1):
+                raise ValueError(f"out must be a unit-stride 1-D tensor of nnz = {nnz} elements")
+            if out.device != G.device:
+                raise ValueError("out must be on the device of G and X")
+        st = self._L.sm_sddmm(h, n_rhs, alpha, _ptr(G), ldg, _ptr(X), ldx, beta, _ptr(out),
+                              _algo(algo), _stream_of(out, stream))
+        check(st, "sm_sddmm")
+        return out
+
+    def _nnz(self) -> int:
+        """nnz of the held matrix, cached per handle like _dims."""
+        h = self._require()
+        if getattr(self, "_nnz_h", None) != h:
+            self._nnz_cache = self.info()["nnz"]
+            self._nnz_h = h
+        return self._nnz_cache
+
+    def csr_device(self, stream=None):
+        """(row_ptr, col_idx, val): new torch tensors on the matrix's device holding its CSR
+        (sm_copy_csr_device; int32, int32, float32), copied on `stream` (None: the current
+        torch stream).  ``from_csr(row_ptr, col_idx, new_val, n_cols)`` takes them back, so
+        values can be updated without a host round trip."""
+        import torch
+        inf = self.info()
+        dev = torch.device("cuda", self.device)
+        rp = torch.empty(inf["n_rows"] + 1, dtype=torch.int32, device=dev)
+        ci = torch.empty(inf["nnz"], dtype=torch.int32, device=dev)
+        va = torch.empty(inf["nnz"], dtype=torch.float32, device=dev)
+        st = self._L.sm_copy_csr_device(self._h, _ptr(rp), _ptr(ci) if inf["nnz"] else 0,
+                                        _ptr(va) if inf["nnz"] else 0, _stream_of(rp, stream))
+        check(st, "sm_copy_csr_device")
+        return rp, ci, va
 
     # ---- the reference's own known-answer test -------------------------------
     @staticmethod
