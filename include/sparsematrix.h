@@ -41,6 +41,9 @@
  *
  * Concurrency: calls on one matrix from several streams or threads are correct;
  * SpMVs that use the matrix's scratch take turns on the device.
+ * sm_set_values / sm_axpy_values are the exception: they write the matrix, so the caller
+ * orders them against products of the same matrix on other streams (an event, or one
+ * stream: a stream's own order is enough).
  *
  * Errors: every call returns sm_status; sm_last_error() gives a message for
  * the calling thread.  Device calls are asynchronous on `stream` (a
@@ -163,6 +166,8 @@ typedef struct sm_info {
     int32_t xband_beta_last;    /* 1: the slab sums are added after beta*y -- y = (((beta*y +
                                    P_0) + P_1) + ...), every P_s summed from -0.0 (band2 / cband
                                    with several slabs); 0: slab 0 starts from beta*y          */
+    int32_t updatable;          /* 1: built with sm_build_opts.updatable (sm_set_values,
+                                   sm_axpy_values apply)                                     */
 } sm_info;
 
 /* ---- library ----------------------------------------------------------- */
@@ -274,6 +279,21 @@ typedef struct sm_build_opts {
                                   the sorted sliced ELL are built on the device where they are
                                   the only layouts wanted (builddev.hip; the same bytes as the
                                   host builders); 1 = always on the host                      */
+    int32_t updatable;         /* 1: the stored values can be replaced in place (sm_set_values,
+                                  sm_axpy_values).  No layout decision then reads the values: the
+                                  matrix is built as if they took more than 255 bit patterns --
+                                  AUTO / SM_LAYOUT_BANDS take band2's 8-byte entries where they
+                                  would take cband, the sliced ELL and the column-chunked ELL their
+                                  plain form -- and every layout that holds its own copy of the
+                                  values also keeps a slot -> term map on the device (4 bytes per
+                                  value slot, counted in sm_info.device_bytes).  What exists only
+                                  in codebook form is SM_ERR_INVALID_ARG with it: SM_LAYOUT_CBAND,
+                                  SM_LAYOUT_SWEEP, hot_cols > 0, merge_stage = 1.  The layouts are
+                                  built by the host builders (as host_build = 1: the device
+                                  builders emit no maps).  sm_build_ref_stream is
+                                  SM_ERR_NOT_SUPPORTED on such a matrix (the stream would go
+                                  stale), so SM_ALGO_NATIVE stays unavailable.  0 (default):
+                                  nothing changes -- the same layouts, bytes and digests       */
 } sm_build_opts;
 
 SM_API void sm_build_opts_init(sm_build_opts *opts);
@@ -302,7 +322,11 @@ SM_API sm_status sm_create_from_csr_device_ex(int64_t n_rows, int64_t n_cols, in
  * the stream is the reference's own byte for byte).  Scratch while building: 24 bytes per term.
  * A dense-index source costs more: its ids are read back from its reference stream on the host
  * (one O(nnz) walk, a row_ptr download, an id upload) and sorted in a second pass of the same
- * kernels, 32 bytes of scratch per term (+ 1 for the source's ids). */
+ * kernels, 32 bytes of scratch per term (+ 1 for the source's ids).
+ * opts->updatable = 1: the result is updatable and also keeps, per term, the term's CSR index in
+ * `src` (int32, nnz entries; one more pass of the same sort), so values given in src's order
+ * update it too (sm_set_values with SM_VALUES_SOURCE); `src` itself need not be updatable.  A
+ * dense-index source is SM_ERR_NOT_SUPPORTED with it: its values are its codebook. */
 SM_API sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts,
                                      sm_stream stream, sm_matrix **out);
 
@@ -342,7 +366,8 @@ SM_API sm_status sm_copy_ref_stream(const sm_matrix *m, uint8_t *pos, uint8_t *v
  * NULL takes the values' distinct bit patterns in CSR order (SM_ERR_NOT_SUPPORTED past
  * 255).  A matrix sm_create_transpose made from a dense-index one, given that one's codebook,
  * uses the ids the index gave the terms instead (equal entries stay apart).
- * A matrix that already holds the encoding is left as it is.  Not concurrent with
+ * A matrix that already holds the encoding is left as it is.  SM_ERR_NOT_SUPPORTED on a matrix
+ * built with sm_build_opts.updatable (the stream would go stale).  Not concurrent with
  * other calls on the matrix.  Additive: the reference cannot hold a matrix without it. */
 SM_API sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t table_size);
 
@@ -352,7 +377,8 @@ SM_API sm_status sm_copy_csr(const sm_matrix *m, int32_t *row_ptr, int32_t *col_
 /* Device copy of the device CSR (row_ptr n_rows+1, col_idx / val nnz) into buffers on the
  * matrix's device, asynchronous on `stream`; any of the three pointers may be NULL to skip that
  * array.  With sm_create_from_csr_device it rebuilds a matrix from updated values without a
- * host round trip. */
+ * host round trip; a matrix built with sm_build_opts.updatable takes new values in place
+ * instead (sm_set_values, sm_axpy_values). */
 SM_API sm_status sm_copy_csr_device(const sm_matrix *m, int32_t *d_row_ptr, int32_t *d_col_idx,
                                     float *d_val, sm_stream stream);
 
@@ -416,6 +442,34 @@ SM_API sm_status sm_spmm(const sm_matrix *m, int32_t n_rhs, float alpha, const f
 SM_API sm_status sm_sddmm(const sm_matrix *m, int32_t n_rhs, float alpha, const float *G, int64_t ldg,
                           const float *X, int64_t ldx, float beta, float *out, sm_algo algo,
                           sm_stream stream);
+
+/* New values for the stored terms, in place (no reference equivalent), for a matrix built with
+ * sm_build_opts.updatable = 1 (SM_ERR_NOT_SUPPORTED otherwise):
+ *   sm_set_values:   val[e] = v[i], bit for bit (NaN payloads, -0.0, denormals);
+ *   sm_axpy_values:  val[e] = fl(val[e] + fl(a * delta[i])) -- two roundings, no fused multiply-add.
+ * `order` says how the array is indexed.  SM_VALUES_OWN: i = e, the matrix's own CSR order (the
+ * order of sm_copy_csr and of sm_sddmm's `out`).  SM_VALUES_SOURCE: the array is in the CSR order
+ * of the matrix this one was transposed from -- term e reads the element of its source term; only
+ * on a matrix sm_create_transpose made with opts->updatable = 1 (SM_ERR_NOT_SUPPORTED otherwise).
+ * Both orders apply the same roundings to the same operands: after the same call on a matrix
+ * and on its transposed companion the two hold the same bits per term.
+ * Afterwards the matrix is what sm_create_from_csr_device_ex builds from (row_ptr, col_idx, the
+ * new values) with the same options: the CSR values, every layout's slots, sm_layout_digest and
+ * every product of every sm_algo, bit for bit.
+ * Arrays: device pointers to nnz floats, 4-byte aligned.  A null `m` is SM_ERR_INVALID_ARG, and so
+ *   is a null array with nnz > 0 (sm_axpy_values: only when a != 0).  nnz == 0: SM_OK, nothing
+ *   launched.  a == 0: SM_OK, nothing launched, `delta` is not read and may be NULL (the
+ *   library's "alpha == 0 skips" rule).
+ * Streams: asynchronous on `stream`: one kernel for the CSR values and one per layout that holds
+ *   its own copy of them.  No allocation, no host synchronisation and no matrix scratch, so the
+ *   call can be captured in a HIP graph.  The call WRITES the matrix: the caller orders it against
+ *   products of the same matrix on other streams; on one stream the stream's order is enough.
+ * The slot -> term maps of device-built layouts are out of scope: an updatable matrix is built by
+ *   the host builders. */
+typedef enum sm_values_order { SM_VALUES_OWN = 0, SM_VALUES_SOURCE = 1 } sm_values_order;
+SM_API sm_status sm_set_values(sm_matrix *m, const float *d_v, sm_values_order order, sm_stream stream);
+SM_API sm_status sm_axpy_values(sm_matrix *m, float a, const float *d_delta, sm_values_order order,
+                                sm_stream stream);
 
 /* AddMatMat (sparse-matrix.cc:139-194) on device pointers:
  * C (m x n, ldc) = alpha * A (m x k, lda) * S + beta * C.

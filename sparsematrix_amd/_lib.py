@@ -29,8 +29,9 @@ SM_ERR_TOO_LARGE = 5
 SM_ERR_INVALID_MATRIX = 6
 SM_ERR_NO_DEVICE = 7
 
-# sm_trans / sm_algo
+# sm_trans / sm_algo / sm_values_order
 SM_NO_TRANS, SM_TRANS = 0, 1
+SM_VALUES_OWN, SM_VALUES_SOURCE = 0, 1
 ALGOS = {"auto": 0, "parity": 1, "stream": 2, "vector": 3, "xband": 4, "sell": 5, "native": 6,
          "exact": 7, "mfma": 8, "merge": 9}
 
@@ -48,6 +49,7 @@ EXPORTS = (
     "sm_multi_destroy", "sm_multi_spmv", "sm_multi_spmm", "sm_multi_spmv_batch",
     "sm_multi_allgather", "sm_multi_set_timing", "sm_multi_last_times", "sm_multi_create_with",
     "sm_debug_seed_handoff", "sm_layout_digest", "sm_sddmm", "sm_copy_csr_device",
+    "sm_set_values", "sm_axpy_values",
 )
 
 SM_UNIQUE_ID_BYTES = 128
@@ -77,7 +79,7 @@ class SmInfo(C.Structure):
         ("sell_slices", C.c_int64), ("sell_codebook", C.c_int32), ("ccsell_chunks", C.c_int32),
         ("hot_cols", C.c_int32), ("sweep_blocks", C.c_int32),
         ("exact_sell_slices", C.c_int64), ("exact_algo", C.c_int32), ("xband_slab0_cols", C.c_int32),
-        ("merge_stage", C.c_int32), ("xband_beta_last", C.c_int32),
+        ("merge_stage", C.c_int32), ("xband_beta_last", C.c_int32), ("updatable", C.c_int32),
     ]
 
 
@@ -94,7 +96,7 @@ class SmBuildOpts(C.Structure):
         ("sell_sigma", C.c_int64), ("relabel", C.c_int32), ("tile_nnz", C.c_int32),
         ("ccsell", C.c_int32), ("ccsell_chunk_log2", C.c_int32), ("hot_cols", C.c_int32),
         ("exact_sell", C.c_int32), ("band_slab0_permille", C.c_int32), ("merge_stage", C.c_int32),
-        ("host_build", C.c_int32),
+        ("host_build", C.c_int32), ("updatable", C.c_int32),
     ]
 
 
@@ -157,6 +159,8 @@ def _declare(L):
         "sm_spmm": ([_vp, _i32, _f32, _vp, _i64, _f32, _vp, _i64, C.c_int, _vp], C.c_int),
         "sm_sddmm": ([_vp, _i32, _f32, _vp, _i64, _vp, _i64, _f32, _vp, C.c_int, _vp], C.c_int),
         "sm_copy_csr_device": ([_vp, _vp, _vp, _vp, _vp], C.c_int),
+        "sm_set_values": ([_vp, _vp, C.c_int, _vp], C.c_int),
+        "sm_axpy_values": ([_vp, _f32, _vp, C.c_int, _vp], C.c_int),
         "sm_addmatmat": ([_vp, _vp, _i32, _i32, _vp, _i32, _f32, _f32, C.c_int, _vp], C.c_int),
         "sm_addmatmat_host": ([_vp, _vp, _i32, _i32, _vp, _i32, _f32, _f32], C.c_int),
         "sm_beta_scale": ([_vp, _i32, _i32, _i32, _f32, _vp], C.c_int),

@@ -74,12 +74,15 @@ def apply(matrix, X, alpha: float = 1.0, values=None):
     on first use and doubles the device memory the matrix holds.
 
     `values` (optional): a float32 tensor of nnz elements on X's device that stands for the
-    matrix's stored values, in CSR order, as the autograd leaf.  It must hold the values the
-    matrix was built from (``matrix.csr_device()[2]``): the forward pass runs on the held matrix
+    matrix's stored values, in CSR order, as the autograd leaf.  It must equal the matrix's
+    current values (``matrix.csr_device()[2]``): the forward pass runs on the held matrix
     and never reads the tensor.  When it requires a gradient, backward returns
     ``matrix.sddmm(grad_Y, X, alpha=alpha)`` for it (X is saved for backward only then), and
-    ``matrix.T`` is not built unless X requires a gradient too.  To step the values, rebuild:
-    ``SparseMatrix.from_csr(row_ptr, col_idx, new_values, n_cols)``."""
+    ``matrix.T`` is not built unless X requires a gradient too.  To step the values of a matrix
+    built with ``opts={"updatable": 1}``, update it in place: ``matrix.axpy_values(-lr,
+    values.grad)`` (a cached ``matrix.T`` follows on the same stream).  Then do the same to the
+    leaf under ``torch.no_grad()`` -- ``values.add_(values.grad * -lr)``, the same two roundings,
+    so the leaf stays equal bit for bit -- or re-read it from ``matrix.csr_device()[2]``."""
     if values is not None:
         import torch
         if not isinstance(values, torch.Tensor) or not values.is_cuda:

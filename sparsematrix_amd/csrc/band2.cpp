@@ -27,6 +27,7 @@ namespace {
 struct TileOut {
     std::vector<int32_t> clo;
     std::vector<uint32_t> ent;
+    std::vector<int32_t> term;   // want_term: 2 per lane entry (Band2Host::term)
     int64_t terms = 0;
     bool ok = true;
 };
@@ -47,8 +48,8 @@ struct Seg {
 // a chunk and the per-row term order are unchanged (only lanes move).  cband
 // (ids != nullptr): lane 0 is the header (the chunk's base row), terms take lanes
 // 1..63 and carry their id, row - base and a continuation flag instead of value bits
-// and rank.
-void emit_chunk(uint32_t *band_ent, int c, const std::vector<Seg> &segs, const int32_t *col,
+// and rank.  band_term (8-byte entries, may be null): the band's slot -> term map.
+void emit_chunk(uint32_t *band_ent, int32_t *band_term, int c, const std::vector<Seg> &segs, const int32_t *col,
                 const float *val, const uint8_t *ids, int32_t clo_al, B2Geom geom) {
     bool used[64] = {false};
     const int cpw = ids != nullptr ? geom.cpw : 2;
@@ -101,7 +102,7 @@ void emit_chunk(uint32_t *band_ent, int c, const std::vector<Seg> &segs, const i
             float v = val[g.s + j];
             uint32_t vb;
             __builtin_memcpy(&vb, &v, 4);
-            e[2 + k] = vb;
+            e[2 + k] = vb; if (band_term) band_term[(size_t)(wave * 64 + lane) * 2 + k] = g.s + j;
         }
         used[lane] = true;
         note(lane, cbits, g.rl, j > 0, cb ? ids[g.s + j] : 0u);
@@ -314,7 +315,7 @@ void balance_chunks(std::vector<std::vector<Seg>> &cs, int nc, const int32_t *co
 }
 
 void build_tile(const int32_t *rp, const int32_t *col, const float *val, const uint8_t *ids,
-                int64_t r0, int64_t r1, int64_t c0, int64_t c1, B2Geom geom, TileOut &out) {
+                int64_t r0, int64_t r1, int64_t c0, int64_t c1, B2Geom geom, bool want_term, TileOut &out) {
 #ifdef SM_DEV
     static const bool kBalance = !(getenv("SM_B2_BAL") && atoi(getenv("SM_B2_BAL")) == 0);   // A/B
 #else
@@ -404,6 +405,8 @@ void build_tile(const int32_t *rp, const int32_t *col, const float *val, const u
         // Emit: segments into chunks in row order.
         const size_t base = out.ent.size();
         out.ent.resize(base + band_words, 0u);   // dummies: word 0 (= dummy ^ dummy), value 0
+        const size_t tbase = out.term.size();
+        if (want_term) out.term.resize(tbase + band_words / 2, -1);
         out.clo.push_back((int32_t)clo_al);
         chunk_segs.assign((size_t)nchunks, {});
         int c = -1, fill = cap;
@@ -417,7 +420,8 @@ void build_tile(const int32_t *rp, const int32_t *col, const float *val, const u
         }
         if (kBalance) balance_chunks(chunk_segs, c + 1, col, (int32_t)clo_al, span);
         for (int k = 0; k <= c; k++)
-            emit_chunk(out.ent.data() + base, k, chunk_segs[(size_t)k], col, val, ids, (int32_t)clo_al, geom);
+            emit_chunk(out.ent.data() + base, want_term ? out.term.data() + tbase : nullptr, k, chunk_segs[(size_t)k],
+                       col, val, ids, (int32_t)clo_al, geom);
         if (!split) clo = chi;   // split: the column's remaining rows go to the next band
     }
     for (int64_t r = 0; r < nr; r++)
@@ -428,8 +432,9 @@ void build_tile(const int32_t *rp, const int32_t *col, const float *val, const u
 
 bool band2_build(const int32_t *rp, const int32_t *col, const float *val, int64_t n_rows,
                  int64_t n_cols, int32_t n_slabs, Band2Host &out, const uint8_t *ids, B2Geom geom,
-                 int32_t slab0_permille) {
+                 int32_t slab0_permille, bool want_term) {
     out = Band2Host();
+    want_term = want_term && !ids;   // codebook words hold ids, not values
     out.codebook = ids != nullptr;
     out.geom = geom;
     if ((!ids && geom.cpw != 2) || geom.cpw < 1 || geom.cpw > 8 ||
@@ -469,7 +474,7 @@ bool band2_build(const int32_t *rp, const int32_t *col, const float *val, int64_
             for (int64_t i = t; i < ntile; i += nthr) {
                 const int64_t b = i / ns, s = i % ns;
                 build_tile(rp, col, val, ids, b * br, std::min<int64_t>(n_rows, (b + 1) * br), slab_lo(s),
-                           slab_lo(s + 1), geom, tiles[(size_t)i]);
+                           slab_lo(s + 1), geom, want_term, tiles[(size_t)i]);
             }
         });
     for (auto &x : th) x.join();
@@ -496,7 +501,9 @@ bool band2_build(const int32_t *rp, const int32_t *col, const float *val, int64_
     for (auto &t : tiles) {
         out.band_clo.insert(out.band_clo.end(), t.clo.begin(), t.clo.end());
         out.ent.insert(out.ent.end(), t.ent.begin(), t.ent.end());
+        out.term.insert(out.term.end(), t.term.begin(), t.term.end());
         std::vector<uint32_t>().swap(t.ent);
+        std::vector<int32_t>().swap(t.term);
     }
     return true;
 }

@@ -82,6 +82,7 @@ void free_xband_dev(XbandDev &h) {
     (void)hipFree(h.d_band_clo);
     (void)hipFree(h.d_table);
     (void)hipFree(h.d_pace);
+    (void)hipFree(h.d_term);
     h = XbandDev();
 }
 
@@ -101,6 +102,8 @@ void free_device(sm_matrix *m) {
     (void)hipFree(m->d_val);
     (void)hipFree(m->d_term_ids);
     m->d_term_ids = nullptr;
+    (void)hipFree(m->d_src_term);
+    m->d_src_term = nullptr;
     (void)hipFree(m->plan.d_tiles);
     (void)hipFree(m->plan.d_merge);
     (void)hipFree(m->plan.d_merge_corner);
@@ -118,7 +121,7 @@ void free_device(sm_matrix *m) {
     for (SellDev *d : {&m->plan.sell, &m->plan.xsell})
         for (void *p : {(void *)d->d_off, (void *)d->d_len, (void *)d->d_row, (void *)d->d_row_len,
                         (void *)d->d_col, (void *)d->d_val, (void *)d->d_table, (void *)d->d_long_rows,
-                        (void *)d->d_long_ptr, (void *)d->d_partials})
+                        (void *)d->d_long_ptr, (void *)d->d_partials, (void *)d->d_term})
             (void)hipFree(p);
     (void)hipFree(m->plan.cc.d_off);
     (void)hipFree(m->plan.cc.d_len);
@@ -127,6 +130,7 @@ void free_device(sm_matrix *m) {
     (void)hipFree(m->plan.cc.d_word);
     (void)hipFree(m->plan.cc.d_val);
     (void)hipFree(m->plan.cc.d_table);
+    (void)hipFree(m->plan.cc.d_term);
     free_native_dev(m->plan.nat);
     (void)hipFree(m->plan.sw.d_block_chunk);
     (void)hipFree(m->plan.sw.d_ent);
@@ -189,6 +193,7 @@ BuildOpts resolve_opts(const sm_build_opts *o) {
         r.band_slab0_permille = d.band_slab0_permille;
         r.merge_stage = d.merge_stage;
         r.host_build = d.host_build;
+        r.updatable = d.updatable;
     }
     if (const char *e = dev_env("SM_XBAND")) r.layout = atoi(e) ? SM_LAYOUT_BANDS : SM_LAYOUT_NO_BANDS;
     if (const char *e = dev_env("SM_XBAND_KIND")) {
@@ -243,6 +248,13 @@ sm_status check_opts(const sm_build_opts *o) {
         return fail(SM_ERR_INVALID_ARG, "band_slab0_permille must be 0 or 500..1000");
     if (r.merge_stage != 0 && r.merge_stage != 1) return fail(SM_ERR_INVALID_ARG, "merge_stage must be 0 or 1");
     if (r.host_build != 0 && r.host_build != 1) return fail(SM_ERR_INVALID_ARG, "host_build must be 0 or 1");
+    if (r.updatable != 0 && r.updatable != 1) return fail(SM_ERR_INVALID_ARG, "updatable must be 0 or 1");
+    if (r.updatable) {   // no codebook forms: their words hold ids chosen from the values
+        if (r.layout == SM_LAYOUT_CBAND || r.layout == SM_LAYOUT_SWEEP)
+            return fail(SM_ERR_INVALID_ARG, "updatable: layout %d exists only in codebook form", r.layout);
+        if (r.hot_cols > 0) return fail(SM_ERR_INVALID_ARG, "updatable: hot_cols exists only in codebook form");
+        if (r.merge_stage == 1) return fail(SM_ERR_INVALID_ARG, "updatable: merge_stage exists only in codebook form");
+    }
     return SM_OK;
 }
 
@@ -285,7 +297,18 @@ XbKind xband_kind_setting(const sm_matrix *m) {
     case SM_LAYOUT_GCB: return kXbGcb;
     default: break;
     }
-    return m->n_cols >= kGcbCols ? kXbGcb : m->n_cols > kGatherCols ? kXbGather : kXbCband;
+    // Updatable matrices take no codebook form: band2's 8-byte entries where cband would serve.
+    return m->n_cols >= kGcbCols ? kXbGcb : m->n_cols > kGatherCols ? kXbGather
+           : m->opts.updatable ? kXbBand2 : kXbCband;
+}
+
+// The slot -> term map of a layout built for an updatable matrix (empty otherwise: nothing
+// allocated), uploaded beside the layout's slots.
+sm_status upload_term_map(sm_matrix *m, const std::vector<int32_t> &term, int32_t **d_term) {
+    if (term.empty()) return SM_OK;
+    SM_TRY_HIP(dev_alloc(d_term, (int64_t)term.size(), m->device_bytes));
+    SM_TRY_HIP(hipMemcpy(*d_term, term.data(), term.size() * 4, hipMemcpyHostToDevice));
+    return SM_OK;
 }
 
 // Sweeping x through LDS (or walking its bands) pays when the L2 -> LDS bytes of
@@ -359,14 +382,15 @@ static sm_status build_band2(sm_matrix *m, XbandDev &d, int64_t n_rows, int64_t 
     if (slabs > 0) want = std::max(1, std::min(16, slabs));
     std::vector<float> table;
     std::vector<uint8_t> ids;
-    const bool cb = kind == kXbCband && codebook_ids(val, nnz, table, ids);
+    const bool upd = m->opts.updatable != 0;   // no layout decision reads the values
+    const bool cb = kind == kXbCband && !upd && codebook_ids(val, nnz, table, ids);
     Band2Host bh;
     B2Geom g = dma3 ? (cb ? kB2Dma3Cb : kB2Dma3B2) : kB2Wide;
     // Bands are fixed slots of g.chunks() * 64 entries: where a slab's density leaves
     // them mostly dummies (wide or very sparse matrices), the padding would cost more HBM
     // bytes than the layout saves -- decline unless forced (SM_LAYOUT_BAND2 / CBAND).
     auto fits = [&](const B2Geom &gg) {
-        if (!band2_build(rp, col, val, n_rows, n_cols, want, bh, cb ? ids.data() : nullptr, gg, slab0_permille))
+        if (!band2_build(rp, col, val, n_rows, n_cols, want, bh, cb ? ids.data() : nullptr, gg, slab0_permille, upd))
             return false;
         return forced || bh.n_bands == 0 ||
                (double)bh.real_terms >= 0.7 * (double)bh.n_bands * gg.chunks() * 64;
@@ -406,6 +430,8 @@ static sm_status build_band2(sm_matrix *m, XbandDev &d, int64_t n_rows, int64_t 
         SM_TRY_HIP(hipMemcpy(d.d_word, bh.ent.data(), (size_t)(bh.n_bands * band_words) * 4,
                              hipMemcpyHostToDevice));
     }
+    if (const sm_status stm = upload_term_map(m, bh.term, &d.d_term)) return stm;
+    d.n_term = (int64_t)bh.term.size() / 2;
     d.kind = cb ? kXbCband : kXbBand2;
     d.threads = 1024;
     d.block_rows = bh.block_rows;
@@ -474,7 +500,8 @@ static sm_status upload_gcb(sm_matrix *m, const int32_t *rp, const int32_t *col,
     int32_t slabs = 1;
     gcb_geometry(m, rows_log2, slabs);
     GcbHost gh;
-    if (!gcb_build(rp, col, val, m->n_rows, m->n_cols, rows_log2, slabs, kGcbMaxWindow, gh)) return SM_OK;
+    if (!gcb_build(rp, col, val, m->n_rows, m->n_cols, rows_log2, slabs, kGcbMaxWindow, gh, m->opts.updatable != 0))
+        return SM_OK;
     XbandDev &d = m->plan.xb;
     const int64_t ntile = (int64_t)gh.n_blocks * gh.n_slabs;
     SM_TRY_HIP(dev_alloc(&d.d_chunk_start, ntile + 1, m->device_bytes));
@@ -487,6 +514,8 @@ static sm_status upload_gcb(sm_matrix *m, const int32_t *rp, const int32_t *col,
         SM_TRY_HIP(hipMemcpy(d.d_word, gh.ent.data(), (size_t)gh.n_bands * kGcbBandWords * 4,
                              hipMemcpyHostToDevice));
     }
+    if (const sm_status stm = upload_term_map(m, gh.term, &d.d_term)) return stm;
+    d.n_term = (int64_t)gh.term.size() / 2;
     return gcb_finish(m, gh);
 }
 
@@ -521,7 +550,7 @@ sm_status upload_xband(sm_matrix *m, const int32_t *rp, const int32_t *col, cons
     // (4 loader waves stage x), all 16 on the exact and gather kinds.
     const int entry_waves = kind == kXbBlocked ? kXbComputeWaves : threads / 64;
     if (!xband_build(rp, col, val, m->n_rows, m->n_cols, bits, entry_waves, xh,
-                     kind == kXbGather)) {
+                     kind == kXbGather, 0, m->opts.updatable != 0)) {
         // The gather kind's wide bands leave 3-4 rank bits: a matrix with longer row
         // segments may still fit the blocked layout (5 bits, 8K-column bands).
         // Only where the blocked kind's own sweep cost still pays (its row blocks
@@ -560,6 +589,8 @@ sm_status upload_xband(sm_matrix *m, const int32_t *rp, const int32_t *col, cons
         SM_TRY_HIP(hipMemcpy(d.d_word, xh.word.data(), xh.word.size() * 4, hipMemcpyHostToDevice));
         SM_TRY_HIP(hipMemcpy(d.d_val, xh.val.data(), xh.val.size() * 4, hipMemcpyHostToDevice));
     }
+    if (const sm_status stm = upload_term_map(m, xh.term, &d.d_term)) return stm;
+    d.n_term = (int64_t)xh.term.size();
     d.kind = kind;
     d.threads = threads;
     d.block_rows = xh.block_rows;
@@ -685,11 +716,12 @@ sm_status upload_sell(sm_matrix *m, const int32_t *rp, const int32_t *col, const
     // patterns and columns < 2^24 -- one 4-byte word per slot instead of column + value.
     std::vector<float> table;
     std::vector<uint8_t> ids;
-    const bool cb = m->opts.sell_codebook != 0 && m->n_cols <= ((int64_t)1 << kSellCbColBits) &&
+    const bool upd = m->opts.updatable != 0;   // the plain form: no decision reads the values
+    const bool cb = m->opts.sell_codebook != 0 && !upd && m->n_cols <= ((int64_t)1 << kSellCbColBits) &&
                     codebook_ids(val, nnz, table, ids);
     if (!cb) std::vector<uint8_t>().swap(ids);
     SellHost sh;
-    sell_build(rp, c, val, m->n_rows, max_len, sh, sigma, streams, cb ? ids.data() : nullptr);
+    sell_build(rp, c, val, m->n_rows, max_len, sh, sigma, streams, cb ? ids.data() : nullptr, upd);
     std::vector<int32_t>().swap(rcol);
     std::vector<uint8_t>().swap(ids);
     if (sh.n_slices == 0) return SM_OK;
@@ -730,6 +762,8 @@ sm_status upload_sell(sm_matrix *m, const int32_t *rp, const int32_t *col, const
         SM_TRY_HIP(hipMemcpy(d.d_col, sh.col.data(), (size_t)sh.padded * 4, hipMemcpyHostToDevice));
         if (!cb) SM_TRY_HIP(hipMemcpy(d.d_val, sh.val.data(), (size_t)sh.padded * 4, hipMemcpyHostToDevice));
     }
+    if (const sm_status stm = upload_term_map(m, sh.term, &d.d_term)) return stm;
+    d.n_term = (int64_t)sh.term.size();
     d.n_slices = sh.n_slices;
     return SM_OK;
 }
@@ -814,13 +848,14 @@ sm_status upload_ccsell(sm_matrix *m, const int32_t *rp, const int32_t *col, con
     const int32_t cl = m->opts.ccsell_chunk_log2 > 0 ? m->opts.ccsell_chunk_log2 : kCcDefaultChunkLog2;
     std::vector<float> table;
     std::vector<uint8_t> ids;
-    const bool cb = m->opts.sell_codebook != 0 && cl <= 24 && codebook_ids(val, m->nnz, table, ids);
+    const bool upd = m->opts.updatable != 0;   // the plain form: no decision reads the values
+    const bool cb = m->opts.sell_codebook != 0 && !upd && cl <= 24 && codebook_ids(val, m->nnz, table, ids);
     if (!cb) std::vector<uint8_t>().swap(ids);
     CcsellHost h;
     // SM_CCSELL_ROWORDER (development A/B): units in row order instead of by length.
     const char *ro = dev_env("SM_CCSELL_ROWORDER");
     const bool by_length = !(ro && atoi(ro) == 1);
-    if (!ccsell_build(rp, col, val, cb ? ids.data() : nullptr, m->n_rows, m->n_cols, cl, h, by_length))
+    if (!ccsell_build(rp, col, val, cb ? ids.data() : nullptr, m->n_rows, m->n_cols, cl, h, by_length, upd))
         return SM_OK;   // not applicable: the sliced ELL serves the matrix
     std::vector<uint8_t>().swap(ids);
     if (h.n_slices == 0) return SM_OK;
@@ -847,6 +882,8 @@ sm_status upload_ccsell(sm_matrix *m, const int32_t *rp, const int32_t *col, con
     SM_TRY_HIP(hipMemcpy(d.d_row_len, h.row_len.data(), h.row_len.size() * 2, hipMemcpyHostToDevice));
     if (h.padded)
         SM_TRY_HIP(hipMemcpy(d.d_word, h.word.data(), (size_t)h.padded * 4, hipMemcpyHostToDevice));
+    if (const sm_status stm = upload_term_map(m, h.term, &d.d_term)) return stm;
+    d.n_term = (int64_t)h.term.size();
     d.n_chunks = h.n_chunks;
     d.chunk_log2 = h.chunk_log2;
     d.chunk_slice = std::move(h.chunk_slice);
@@ -1470,7 +1507,9 @@ static sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_
     // ELL, and no column-chunked ELL once the relabeling is decided (its builder runs on the
     // host).  R-MAT 24: the host path took 5.4 s.
     bool dev_done = false;
-    const bool dev_ok = st == SM_OK && m->opts.host_build == 0 && !want_sweep(m) && m->opts.hot_cols <= 0 &&
+    // An updatable matrix is built as host_build = 1: only the host builders emit the slot -> term maps.
+    const bool dev_ok = st == SM_OK && m->opts.host_build == 0 && m->opts.updatable == 0 && !want_sweep(m) &&
+                        m->opts.hot_cols <= 0 &&
                         m->opts.sell_sigma == 0 && m->opts.sell_streams <= 1 && m->opts.exact_sell != 1;
     // The gathered chunk bands on the device (builddev_gcb.hip; config 5: 15 s on the host path).
     // Declined (a row's columns not ascending, size limits): the host path below decides.
@@ -1642,6 +1681,8 @@ sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts, s
     if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
     hipStream_t s = (hipStream_t)stream;
     auto m = new_matrix(src->device, opts);
+    if (m->opts.updatable && src->from_index)
+        return fail(SM_ERR_NOT_SUPPORTED, "updatable transpose of a dense-index matrix: its values are its codebook");
     m->n_rows = src->n_cols;
     m->n_cols = src->n_rows;
     m->nnz = src->nnz;
@@ -1672,6 +1713,16 @@ sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts, s
             if (e != hipSuccess) st = hip_fail(e, "sm_create_transpose (term ids)");
         }
         (void)hipFree(own);
+    }
+    if (st == SM_OK && m->opts.updatable) {   // values given in src's CSR order reach this matrix too
+        m->has_src_term = true;
+        if (m->nnz > 0) {
+            hipError_t e = dev_alloc(&m->d_src_term, m->nnz, m->device_bytes);
+            if (e == hipSuccess)
+                e = transpose_terms_device(src->d_row_ptr, src->d_col, src->n_rows, src->n_cols, src->nnz,
+                                           m->d_src_term, s);
+            if (e != hipSuccess) st = hip_fail(e, "sm_create_transpose (source terms)");
+        }
     }
     if (st == SM_OK) st = finish_from_device_csr(m.get(), s, true);
     if (st != SM_OK) {
@@ -1736,6 +1787,7 @@ sm_status sm_get_info_ex(const sm_matrix *m, sm_info *out, size_t info_bytes) {
     info->xband_beta_last = SM_B2_BL && m->plan.xb.n_blocks > 0 && m->plan.xb.n_slabs > 1 &&
                             (m->plan.xb.kind == kXbBand2 || m->plan.xb.kind == kXbCband);
     info->device_bytes = m->device_bytes;
+    info->updatable = m->opts.updatable ? 1 : 0;
     info->col_relabel = m->plan.n_relabel > 0 ? 1 : 0;
     info->sell_slices = m->plan.sell.n_slices;
     info->sell_codebook = m->plan.sell.d_table != nullptr || m->plan.cc.d_table != nullptr;
@@ -1836,6 +1888,8 @@ sm_status sm_copy_ref_stream(const sm_matrix *m, uint8_t *pos, uint8_t *val, int
 
 sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t table_size) {
     if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (m->opts.updatable)
+        return fail(SM_ERR_NOT_SUPPORTED, "updatable matrix: the stream would go stale with the next update");
     if (m->has_ref) return SM_OK;
     if (table && (table_size < 0 || table_size > 255))
         return fail(SM_ERR_INVALID_ARG, "table_size %d not in [0, 255]", table_size);
@@ -2152,6 +2206,46 @@ sm_status sm_sddmm(const sm_matrix *m, int32_t n_rhs, float alpha, const float *
                               beta, s);
     e = after_launch(e, s, "sm_sddmm");
     return e == hipSuccess ? SM_OK : hip_fail(e, "sm_sddmm launch");
+}
+
+// The CSR step, then one refresh per layout that holds its own copy of the values
+// (kernels_values.hip): launches only, so the call can be captured.
+static sm_status update_values(sm_matrix *m, bool axpy, float a, const float *d_in, sm_values_order order,
+                               sm_stream stream, const char *what) {
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (order != SM_VALUES_OWN && order != SM_VALUES_SOURCE) return fail(SM_ERR_INVALID_ARG, "bad sm_values_order");
+    if (!m->opts.updatable)
+        return fail(SM_ERR_NOT_SUPPORTED, "%s: the matrix was not built with sm_build_opts.updatable", what);
+    if (order == SM_VALUES_SOURCE && !m->has_src_term)
+        return fail(SM_ERR_NOT_SUPPORTED, "%s: SM_VALUES_SOURCE needs a matrix made by sm_create_transpose", what);
+    if (m->nnz == 0 || (axpy && a == 0.0f)) return SM_OK;
+    if (!d_in) return fail(SM_ERR_INVALID_ARG, "%s: null array", what);
+    DeviceGuard g(m->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    const Plan &p = m->plan;
+    hipError_t e = launch_values_csr(m->nnz, axpy, a, d_in, order == SM_VALUES_SOURCE ? m->d_src_term : nullptr,
+                                     m->d_val, s);
+    if (e == hipSuccess && p.xb.d_term) {
+        if (p.xb.kind == kXbBand2 || p.xb.kind == kXbGcb)
+            e = launch_refresh_entry(p.xb.n_term, p.xb.d_term, m->d_val, p.xb.d_word, s);
+        else
+            e = launch_refresh_plain(p.xb.n_term, p.xb.d_term, m->d_val, p.xb.d_val, s);
+    }
+    for (const SellDev *d : {&p.sell, &p.xsell})
+        if (e == hipSuccess && d->d_term) e = launch_refresh_plain(d->n_term, d->d_term, m->d_val, d->d_val, s);
+    if (e == hipSuccess && p.cc.d_term) e = launch_refresh_plain(p.cc.n_term, p.cc.d_term, m->d_val, p.cc.d_val, s);
+    e = after_launch(e, s, what);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return SM_OK;
+}
+
+sm_status sm_set_values(sm_matrix *m, const float *d_v, sm_values_order order, sm_stream stream) {
+    return update_values(m, false, 0.0f, d_v, order, stream, "sm_set_values");
+}
+
+sm_status sm_axpy_values(sm_matrix *m, float a, const float *d_delta, sm_values_order order, sm_stream stream) {
+    return update_values(m, true, a, d_delta, order, stream, "sm_axpy_values");
 }
 
 sm_status sm_copy_csr_device(const sm_matrix *m, int32_t *d_row_ptr, int32_t *d_col_idx, float *d_val,

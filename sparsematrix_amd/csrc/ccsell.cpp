@@ -27,8 +27,9 @@ struct Unit {
 
 bool ccsell_build(const int32_t *rp, const int32_t *col, const float *val, const uint8_t *ids,
                   int64_t n_rows, int64_t n_cols, int32_t chunk_log2, CcsellHost &out,
-                  bool by_length) {
+                  bool by_length, bool want_term) {
     out = CcsellHost();
+    want_term = want_term && !ids;
     if (n_rows <= 0 || n_cols <= 0 || chunk_log2 < 8 || chunk_log2 > 30) return false;
     if (ids && chunk_log2 > 24) return false;               // column bits + 8-bit id
     if (n_rows >= ((int64_t)1 << 31)) return false;
@@ -137,6 +138,7 @@ bool ccsell_build(const int32_t *rp, const int32_t *col, const float *val, const
     out.padded = slots;
     out.word.assign((size_t)slots, 0u);
     if (!ids) out.val.assign((size_t)slots, 0.0f);
+    if (want_term) out.term.assign((size_t)slots, -1);
     const uint32_t cmask = (uint32_t)((1ull << chunk_log2) - 1);
     auto fill = [&](int64_t s0, int64_t s1) {
         for (int64_t s = s0; s < s1; s++) {
@@ -155,7 +157,8 @@ bool ccsell_build(const int32_t *rp, const int32_t *col, const float *val, const
                 }
                 if (!ids) {
                     float *v = out.val.data() + out.off[(size_t)s] + l;
-                    for (int32_t j = 0; j < u.n; j++) v[(size_t)j * kSellLanes] = val[u.start + j];
+                    int32_t *t = want_term ? out.term.data() + out.off[(size_t)s] + l : nullptr;
+                    for (int32_t j = 0; j < u.n; j++) { v[(size_t)j * kSellLanes] = val[u.start + j]; if (t) t[(size_t)j * kSellLanes] = u.start + j; }
                 }
             }
         }

@@ -36,14 +36,16 @@ struct CcsellHost {
     std::vector<uint16_t> row_len;      // n_slices * 64
     std::vector<uint32_t> word;         // padded slots
     std::vector<float> val;             // padded slots (plain form only)
+    std::vector<int32_t> term;          // want_term (plain form): per slot its term's CSR index, -1 = padding
 };
 
 // ids != nullptr: codebook form (requires chunk_log2 <= 24).  Returns false when a
 // unit would exceed kCcMaxUnit terms or the columns are not ascending per row.
 // by_length = false keeps each chunk's units in row order (the y accesses of a slice
-// then fall in a short window of rows) instead of sorting them by length.
+// then fall in a short window of rows) instead of sorting them by length.  want_term: also the
+// slot -> term map (CcsellHost::term; plain form only).
 bool ccsell_build(const int32_t *row_ptr, const int32_t *col, const float *val,
                   const uint8_t *ids, int64_t n_rows, int64_t n_cols, int32_t chunk_log2,
-                  CcsellHost &out, bool by_length = true);
+                  CcsellHost &out, bool by_length = true, bool want_term = false);
 
 }  // namespace smamd

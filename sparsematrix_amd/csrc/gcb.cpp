@@ -25,6 +25,7 @@ struct Term {
 struct TileOut {
     std::vector<int32_t> clo;
     std::vector<uint32_t> ent;
+    std::vector<int32_t> term;   // want_term: 2 per lane entry (GcbHost::term)
     int64_t terms = 0;
     bool ok = true;
 };
@@ -66,7 +67,7 @@ void segments(const Term *t, int64_t a, int64_t b, std::vector<Term> &scratch, s
 }
 
 void build_tile(const int32_t *rp, const int32_t *col, const float *val, int64_t r0, int64_t r1,
-                int64_t c0, int64_t c1, int32_t window, TileOut &out) {
+                int64_t c0, int64_t c1, int32_t window, bool want_term, TileOut &out) {
     std::vector<Term> t;
     for (int64_t r = r0; r < r1; r++) {
         const int32_t *a = col + rp[r], *z = col + rp[r + 1];
@@ -101,6 +102,8 @@ void build_tile(const int32_t *rp, const int32_t *col, const float *val, int64_t
         // Emit: per chunk, lane 0 the header, then the segments' terms in order.
         const size_t base = out.ent.size();
         out.ent.resize(base + kGcbBandWords, 0u);
+        const size_t tbase = out.term.size();
+        if (want_term) out.term.resize(tbase + kGcbBandWords / 2, -1);
         out.clo.push_back(clo);
         uint32_t *band = out.ent.data() + base;
         int lane_next[kGcbChunks];
@@ -118,12 +121,13 @@ void build_tile(const int32_t *rp, const int32_t *col, const float *val, int64_t
             }
             for (int32_t j = 0; j < g.n; j++) {
                 const Term &m = scratch[(size_t)(g.first + j)];
-                uint32_t *e = slot(lane_next[c]++);
+                const int lane = lane_next[c]++;
+                uint32_t *e = slot(lane);
                 e[k] = (uint32_t)(m.col - clo) | ((uint32_t)(g.rl - cbase[c]) << kGcbColBits) | kGcbLive |
                        (j > 0 ? kGcbCont : 0u);
                 uint32_t vb;
                 memcpy(&vb, &val[m.e], 4);
-                e[2 + k] = vb;
+                e[2 + k] = vb; if (want_term) out.term[tbase + (size_t)(wave * 64 + lane) * 2 + k] = m.e;
             }
         }
         out.terms += b - a;
@@ -134,7 +138,7 @@ void build_tile(const int32_t *rp, const int32_t *col, const float *val, int64_t
 }  // namespace
 
 bool gcb_build(const int32_t *rp, const int32_t *col, const float *val, int64_t n_rows, int64_t n_cols,
-               int rows_log2, int32_t n_slabs, int32_t window, GcbHost &out) {
+               int rows_log2, int32_t n_slabs, int32_t window, GcbHost &out, bool want_term) {
     out = GcbHost();
     if (rows_log2 < 6 || rows_log2 > 15 || window < 64 || window > kGcbMaxWindow) return false;
     if (n_rows <= 0 || n_cols <= 0 || n_slabs < 1 || n_cols >= ((int64_t)1 << 30)) return false;
@@ -157,7 +161,7 @@ bool gcb_build(const int32_t *rp, const int32_t *col, const float *val, int64_t 
             for (int64_t i = k; i < ntile; i += nthr) {
                 const int64_t b = i / ns, s = i % ns;
                 build_tile(rp, col, val, b * br, std::min<int64_t>(n_rows, (b + 1) * br), s * sc,
-                           std::min<int64_t>(n_cols, (s + 1) * sc), window, tiles[(size_t)i]);
+                           std::min<int64_t>(n_cols, (s + 1) * sc), window, want_term, tiles[(size_t)i]);
             }
         });
     for (auto &x : th) x.join();
@@ -187,7 +191,9 @@ bool gcb_build(const int32_t *rp, const int32_t *col, const float *val, int64_t 
     for (auto &x : tiles) {
         out.band_clo.insert(out.band_clo.end(), x.clo.begin(), x.clo.end());
         out.ent.insert(out.ent.end(), x.ent.begin(), x.ent.end());
+        out.term.insert(out.term.end(), x.term.begin(), x.term.end());
         std::vector<uint32_t>().swap(x.ent);
+        std::vector<int32_t>().swap(x.term);
     }
     return true;
 }

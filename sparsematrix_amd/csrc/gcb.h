@@ -46,11 +46,15 @@ struct GcbHost {
     std::vector<int32_t> tile_band_start;   // n_blocks * n_slabs + 1 (tile t = b * S + s)
     std::vector<int32_t> band_clo;          // first column of each band
     std::vector<uint32_t> ent;              // kGcbBandWords per band
+    // want_term: per lane entry {word, word, value, value} the CSR indices of its two values,
+    // -1 = header / dummy -- 2 per entry, ent.size() / 2 in all; empty otherwise.
+    std::vector<int32_t> term;
 };
 
 // Returns false when the layout does not apply (unsorted or repeated columns in a row,
 // size limits).  rows_log2 <= 15 (the block's sums in LDS), window <= 2^18.
 bool gcb_build(const int32_t *row_ptr, const int32_t *col, const float *val, int64_t n_rows,
-               int64_t n_cols, int rows_log2, int32_t n_slabs, int32_t window, GcbHost &out);
+               int64_t n_cols, int rows_log2, int32_t n_slabs, int32_t window, GcbHost &out,
+               bool want_term = false);
 
 }  // namespace smamd

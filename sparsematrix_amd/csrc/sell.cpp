@@ -12,8 +12,10 @@
 namespace smamd {
 
 void sell_build(const int32_t *rp, const int32_t *col, const float *val, int64_t n_rows,
-                int32_t max_len, SellHost &out, int64_t sigma, int streams, const uint8_t *ids) {
+                int32_t max_len, SellHost &out, int64_t sigma, int streams, const uint8_t *ids,
+                bool want_term) {
     out = SellHost();
+    want_term = want_term && !ids;
     // Units: a row of <= max_len terms, or one segment of a longer row.
     struct Unit {
         int32_t row, start, n, part;   // part >= 0: segment partial index
@@ -85,6 +87,7 @@ void sell_build(const int32_t *rp, const int32_t *col, const float *val, int64_t
     out.padded = slots;
     out.col.assign((size_t)slots, 0);
     if (!ids) out.val.assign((size_t)slots, 0.0f);
+    if (want_term) out.term.assign((size_t)slots, -1);
     // Fill the slots, slices split across threads (disjoint lanes: no sharing).
     auto fill = [&](int64_t s0, int64_t s1) {
         for (int64_t s = s0; s < s1; s++) {
@@ -102,9 +105,10 @@ void sell_build(const int32_t *rp, const int32_t *col, const float *val, int64_t
                     continue;
                 }
                 float *v = out.val.data() + out.off[(size_t)s] + l;
+                int32_t *t = want_term ? out.term.data() + out.off[(size_t)s] + l : nullptr;
                 for (int32_t j = 0; j < u.n; j++) {
                     c[(size_t)j * kSellLanes] = col[u.start + j];
-                    v[(size_t)j * kSellLanes] = val[u.start + j];
+                    v[(size_t)j * kSellLanes] = val[u.start + j]; if (t) t[(size_t)j * kSellLanes] = u.start + j;
                 }
             }
         }

@@ -28,6 +28,7 @@ struct SellHost {
     std::vector<int32_t> row_len;       // n_slices * 64: that row's length
     std::vector<int32_t> col;           // padded slots (codebook: words, see below)
     std::vector<float> val;             // padded slots (empty with codebook ids)
+    std::vector<int32_t> term;          // want_term (plain form): per slot its term's index into col / val, -1 = padding
     std::vector<int32_t> long_rows;     // rows split in segments
     std::vector<int32_t> long_ptr;      // long_rows.size() + 1: their partials
 };
@@ -42,10 +43,11 @@ struct SellHost {
 // slices (length 0, every lane -1).  ids != nullptr (codebook sell, every column <
 // 2^24): each slot is one word, column | id << 24 (the value's codebook id, as the
 // reference stores it: sparse-matrix.h:46-52), and `val` stays empty -- 4 bytes per
-// slot instead of 8; padding words are 0 (never added).
+// slot instead of 8; padding words are 0 (never added).  want_term: also the slot -> term map
+// (SellHost::term; plain form only, for matrices whose values are updated in place).
 constexpr int kSellCbColBits = 24;
 void sell_build(const int32_t *row_ptr, const int32_t *col, const float *val, int64_t n_rows,
                 int32_t max_len, SellHost &out, int64_t sigma = 0, int streams = 1,
-                const uint8_t *ids = nullptr);
+                const uint8_t *ids = nullptr, bool want_term = false);
 
 }  // namespace smamd

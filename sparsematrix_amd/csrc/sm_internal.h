@@ -57,6 +57,7 @@ struct BuildOpts {
     int32_t band_slab0_permille = 0;   // 0 auto (sm_build_opts.band_slab0_permille)
     int32_t merge_stage = 0;           // sm_build_opts.merge_stage
     int32_t host_build = 0;            // sm_build_opts.host_build
+    int32_t updatable = 0;             // sm_build_opts.updatable
 };
 
 // Row tile: rows [r0, r1) whose terms fit one LDS tile.  flags bit0: the tile
@@ -94,6 +95,12 @@ struct XbandDev {
     // gcb kind: column pacing words (kernels_gcb.hip), 8 x (1 + pace_k) monotonic counters.
     int32_t *d_pace = nullptr;
     int32_t pace_k = 0;
+    // Updatable matrices (sm_build_opts.updatable): the slot -> term map of the kinds that hold
+    // their own copy of the values.  exact / blocked / gather: one entry per d_val slot
+    // (n_term = the slots); band2 / gcb: two per 16-byte lane entry of d_word (n_term = the
+    // entries).  -1: a dummy slot.
+    int32_t *d_term = nullptr;
+    int64_t n_term = 0;
 };
 
 // Device copy of the sorted sliced-ELL layout (sell.h).
@@ -114,6 +121,9 @@ struct SellDev {
     int32_t *d_long_rows = nullptr;   // n_long
     int32_t *d_long_ptr = nullptr;    // n_long + 1 offsets into d_partials
     float *d_partials = nullptr;      // one per segment (one SpMV in flight per matrix)
+    // Updatable matrices: per d_val slot the CSR index of its term, -1 = padding (n_term slots).
+    int32_t *d_term = nullptr;
+    int64_t n_term = 0;
 };
 
 // Device copy of the column-chunked sorted sliced-ELL layout (ccsell.h).
@@ -129,6 +139,9 @@ struct CcsellDev {
     float *d_val = nullptr;           // plain form
     float *d_table = nullptr;         // codebook form
     int32_t table_size = 0;
+    // Updatable matrices: per d_val slot the CSR index of its term, -1 = padding (n_term slots).
+    int32_t *d_term = nullptr;
+    int64_t n_term = 0;
 };
 
 // Device copy of the reference's own stream (native.hip): uint8 deltas + ids, each
@@ -340,6 +353,18 @@ hipError_t transpose_csr_device(const int32_t *rp, const int32_t *col, const flo
 // transposition above gives the terms.
 hipError_t transpose_ids_device(const int32_t *rp, const int32_t *col, const uint8_t *ids, int64_t n_rows,
                                 int64_t n_cols, int64_t nnz, uint8_t *t_ids, hipStream_t s);
+// The transposition's term map: t_src[j] = the CSR index in B of term j of B^T (sm_set_values
+// with SM_VALUES_SOURCE) -- the term index carried through the same pack / sort / unpack.
+hipError_t transpose_terms_device(const int32_t *rp, const int32_t *col, int64_t n_rows, int64_t n_cols,
+                                  int64_t nnz, int32_t *t_src, hipStream_t s);
+// In-place value updates (kernels_values.hip).  CSR step: val[e] = in[i] (axpy: fl(val[e] +
+// fl(a * in[i]))), i = e, or src[e] when `src` is given.  Refresh steps: slot s takes val[map[s]]
+// where map[s] >= 0 -- plain float slots, or the value words 2-3 of 16-byte lane entries (two map
+// entries per lane entry).
+hipError_t launch_values_csr(int64_t nnz, bool axpy, float a, const float *in, const int32_t *src, float *val,
+                             hipStream_t s);
+hipError_t launch_refresh_plain(int64_t n_slots, const int32_t *map, const float *val, float *slot, hipStream_t s);
+hipError_t launch_refresh_entry(int64_t n_ent, const int32_t *map, const float *val, uint32_t *ent, hipStream_t s);
 hipError_t launch_validate(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t *rp,
                            const int32_t *col, int32_t *d_flag, hipStream_t s);
 // Dense decode: out is zeroed by the caller.  b_layout: out[row*stride+col]
@@ -378,6 +403,10 @@ struct sm_matrix {
     // they index `table` and exist only while has_ref is false (sm_build_ref_stream frees them:
     // the stream then holds the ids, and sm_create_transpose reads them back from it).
     uint8_t *d_term_ids = nullptr;
+    // Updatable matrix made by sm_create_transpose: per term its CSR index in the source matrix
+    // (nnz entries), so values given in the source's order reach it (SM_VALUES_SOURCE).
+    int32_t *d_src_term = nullptr;
+    bool has_src_term = false;   // (also true with nnz == 0, where there is nothing to allocate)
     std::vector<uint8_t> pos, val;
     std::vector<int32_t> panel_row_off, panel_col_off;
     std::vector<int64_t> panel_begin, panel_end;

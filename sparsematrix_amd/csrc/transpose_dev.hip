@@ -25,7 +25,8 @@
 //
 // transpose_ids_device: a CopyForm-built matrix's codebook ids (one byte per term) in the new
 // order -- the same pack / sort / unpack with the widened id as the "value" (8 more bytes per
-// term of scratch; such matrices are bounded by their dense index).
+// term of scratch; such matrices are bounded by their dense index).  transpose_terms_device: the
+// terms' own indices the same way (sm_build_opts.updatable: values given in the source's order).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -76,6 +77,10 @@ __global__ __launch_bounds__(256) void tr_unpack_kernel(int64_t nnz, const unsig
 __global__ __launch_bounds__(256) void tr_widen_kernel(int64_t nnz, const uint8_t *__restrict__ ids,
                                                        uint32_t *__restrict__ wide) {
     GS_LOOP(e, nnz) wide[e] = ids[e];
+}
+
+__global__ __launch_bounds__(256) void tr_iota_kernel(int64_t nnz, uint32_t *__restrict__ idx) {
+    GS_LOOP(e, nnz) idx[e] = (uint32_t)e;
 }
 
 __global__ __launch_bounds__(256) void tr_narrow_kernel(int64_t nnz, const uint32_t *__restrict__ wide,
@@ -185,6 +190,26 @@ hipError_t transpose_ids_device(const int32_t *rp, const int32_t *col, const uin
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+}
+
+hipError_t transpose_terms_device(const int32_t *rp, const int32_t *col, int64_t n_rows, int64_t n_cols,
+                                  int64_t nnz, int32_t *t_src, hipStream_t s) {
+    if (nnz <= 0) return hipSuccess;
+    hipError_t e = hipSuccess;
+    {
+        Tmp t;
+        uint32_t *idx = nullptr;
+        e = t.alloc(&idx, nnz);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(tr_iota_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, idx);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess)   // the index rides as the bits of the 4-byte "value", straight into t_src
+            e = transpose_body(rp, col, reinterpret_cast<const float *>(idx), n_rows, n_cols, nnz, nullptr, nullptr,
+                               reinterpret_cast<float *>(t_src), s);
     }
     if (e != hipSuccess) (void)hipGetLastError();
     return e;

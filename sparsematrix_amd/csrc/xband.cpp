@@ -34,20 +34,20 @@ namespace smamd {
 
 static bool xband_build_fixed(const int32_t *rp, const int32_t *col, const float *val,
                               int64_t n_rows, int64_t n_cols, int32_t block_rows, XbBits bits,
-                              int waves, bool col_order, XbandHost &out);
+                              int waves, bool col_order, XbandHost &out, bool want_term);
 
 // Largest block height (<= 2^bits.row, >= 64) whose bands fit the kernel's
 // register capacity (kXbMaxCap chunks per wave per band).
 bool xband_build(const int32_t *rp, const int32_t *col, const float *val, int64_t n_rows,
                  int64_t n_cols, XbBits bits, int waves, XbandHost &out, bool col_order,
-                 int32_t start_rows) {
+                 int32_t start_rows, bool want_term) {
     if (bits.col < 8 || bits.row < 6 || bits.rank < 2 || bits.col + bits.rank + bits.row != 32)
         return false;
     int32_t br0 = 1 << bits.row;
     while (start_rows > 0 && br0 > start_rows && br0 > 64) br0 /= 2;
     for (int32_t br = br0; br >= 64; br /= 2) {
         out.too_dense = false;
-        if (xband_build_fixed(rp, col, val, n_rows, n_cols, br, bits, waves, col_order, out))
+        if (xband_build_fixed(rp, col, val, n_rows, n_cols, br, bits, waves, col_order, out, want_term))
             return true;
         if (!out.too_dense) return false;   // not a capacity problem: halving will not help
     }
@@ -56,7 +56,7 @@ bool xband_build(const int32_t *rp, const int32_t *col, const float *val, int64_
 
 static bool xband_build_fixed(const int32_t *rp, const int32_t *col, const float *val,
                               int64_t n_rows, int64_t n_cols, int32_t block_rows, XbBits bits,
-                              int waves, bool col_order, XbandHost &out) {
+                              int waves, bool col_order, XbandHost &out, bool want_term) {
     out = XbandHost();
     if (n_rows <= 0 || n_cols <= 0) return false;
     const int32_t band_cols = 1 << bits.col;
@@ -152,6 +152,7 @@ static bool xband_build_fixed(const int32_t *rp, const int32_t *col, const float
     }
     out.word.assign((size_t)(total * 64), 0u);   // dummies (stored XOR dummy_word)
     out.val.assign((size_t)(total * 64), 0.0f);
+    if (want_term) out.term.assign((size_t)(total * 64), -1);
 
     // Lanes inside a chunk.  Order matters only within a row's segment (the
     // kernel passes running sums from lane to lane and the last lane writes), so
@@ -169,7 +170,7 @@ static bool xband_build_fixed(const int32_t *rp, const int32_t *col, const float
             out.word[(size_t)slot] = (cb | ((uint32_t)k << bits.col) |
                                       ((uint32_t)g.rl << (bits.col + bits.rank))) ^
                                      bits.dummy_word();
-            out.val[(size_t)slot] = val[g.s + k];
+            out.val[(size_t)slot] = val[g.s + k]; if (want_term) out.term[(size_t)slot] = g.s + k;
             used[lane] = true;
         };
         for (const Seg &g : segs)

@@ -57,6 +57,7 @@ struct XbandHost {
     std::vector<int64_t> chunk_start;          // n_blocks * n_bands + 1
     std::vector<uint32_t> word;                // 64 per chunk, XOR bits.dummy_word()
     std::vector<float> val;
+    std::vector<int32_t> term;                 // want_term: per slot the CSR index of its term, -1 = dummy
 };
 
 // Returns false when the matrix does not fit the layout (a row segment longer
@@ -64,10 +65,11 @@ struct XbandHost {
 // for 64-row blocks, or size limits).  The block height starts at 2^bits.row (or
 // `start_rows` when smaller and > 0) and halves while a band overflows the
 // kernel's register capacity.  col_order: a band's segments are listed by their
-// first column instead of by row (the gather kind).
+// first column instead of by row (the gather kind).  want_term: also the slot -> term map
+// (XbandHost::term, for matrices whose values are updated in place); empty otherwise.
 bool xband_build(const int32_t *row_ptr, const int32_t *col, const float *val, int64_t n_rows,
                  int64_t n_cols, XbBits bits, int waves, XbandHost &out, bool col_order = false,
-                 int32_t start_rows = 0);
+                 int32_t start_rows = 0, bool want_term = false);
 
 }  // namespace smamd
 
@@ -148,6 +150,9 @@ struct Band2Host {
     std::vector<int32_t> tile_band_start;   // n_blocks * n_slabs + 1 (tile t = b * S + s)
     std::vector<int32_t> band_clo;          // first column of each band's window (multiple of 4)
     std::vector<uint32_t> ent;              // 4096 per band
+    // want_term (8-byte entries only): per lane entry {word, word, value, value} the CSR indices
+    // of its two values, -1 = dummy -- 2 per entry, ent.size() / 2 in all; empty otherwise.
+    std::vector<int32_t> term;
     int64_t real_terms = 0;                 // for the padding report
 };
 
@@ -160,7 +165,7 @@ struct Band2Host {
 constexpr int32_t kB2Slab0Permille = 1000;
 bool band2_build(const int32_t *row_ptr, const int32_t *col, const float *val, int64_t n_rows,
                  int64_t n_cols, int32_t n_slabs, Band2Host &out, const uint8_t *ids = nullptr,
-                 B2Geom geom = kB2Wide, int32_t slab0_permille = 1000);
+                 B2Geom geom = kB2Wide, int32_t slab0_permille = 1000, bool want_term = false);
 
 // Codebook of a value array: table[ids[e]] has the bits of val[e] for every e; false
 // when there are more than 255 distinct bit patterns (table then undefined).

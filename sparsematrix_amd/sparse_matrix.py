@@ -220,6 +220,8 @@ class SparseMatrix:
         build_ref_stream adds it).  Synchronises `stream` (None: the current torch stream)."""
         h0 = self._require()
         t = SparseMatrix(device=self.device)
+        if self._updatable():   # the companion of an updatable matrix follows its updates
+            opts = dict(opts or {}, updatable=1)
         o = _lib.build_opts(**(opts or {}))
         h = C.c_void_p()
         st = self._L.sm_create_transpose(h0, C.byref(o), _stream_of(self, stream), C.byref(h))
@@ -433,15 +435,64 @@ class SparseMatrix:
         """nnz of the held matrix, cached per handle like _dims."""
         h = self._require()
         if getattr(self, "_nnz_h", None) != h:
-            self._nnz_cache = self.info()["nnz"]
+            inf = self.info()
+            self._nnz_cache = inf["nnz"]
+            self._upd_cache = bool(inf["updatable"])
             self._nnz_h = h
         return self._nnz_cache
+
+    def _updatable(self) -> bool:
+        """Built with opts updatable=1 (cached per handle like _nnz)."""
+        self._nnz()
+        return self._upd_cache
+
+    # ---- updating the stored values in place ----------------------------------
+    def _values_operand(self, t, name: str) -> None:
+        nnz = self._nnz()
+        _check_dev(t, nnz, name)
+        if t.dim() != 1 or t.numel() != nnz or (nnz > 1 and t.stride(0) != 1):
+            raise ValueError(f"{name} must be a unit-stride 1-D tensor of nnz = {nnz} elements")
+        if t.device.index != self.device:
+            raise ValueError(f"{name} must be on the matrix's device")
+
+    def set_values(self, val, stream=None) -> None:
+        """val[e] = val_new[e], bit for bit, for every stored term e in CSR order (sm_set_values),
+        on a matrix built with ``opts={"updatable": 1}``: afterwards the matrix is what from_csr
+        builds from the new values with the same options, every layout and product bit for bit.
+        `val`: nnz float32 elements on the matrix's device.  Asynchronous on `stream` (None: the
+        current torch stream), no allocation and no synchronisation, so it can be captured in a
+        graph.  A cached transposed companion (T) is updated on the same stream.  The call writes
+        the matrix: order it against products of this matrix on other streams."""
+        h = self._require()
+        self._values_operand(val, "val")
+        s = _stream_of(self, stream)
+        check(self._L.sm_set_values(h, _ptr(val), _lib.SM_VALUES_OWN, s), "sm_set_values")
+        if self._t is not None:
+            check(self._L.sm_set_values(self._t._require(), _ptr(val), _lib.SM_VALUES_SOURCE, s),
+                  "sm_set_values (T)")
+
+    def axpy_values(self, a: float, delta, stream=None) -> None:
+        """val[e] = fl(val[e] + fl(a * delta[e])) for every stored term e in CSR order
+        (sm_axpy_values; two roundings, no fused multiply-add), on a matrix built with
+        ``opts={"updatable": 1}`` -- an optimiser step on the values, e.g.
+        ``m.axpy_values(-lr, grad)`` with the gradient sddmm gives.  a == 0 does nothing and
+        `delta` may then be None.  Stream behaviour and the companion T as for set_values."""
+        h = self._require()
+        a = float(a)
+        if a != 0.0 or delta is not None:
+            self._values_operand(delta, "delta")
+        s = _stream_of(self, stream)
+        check(self._L.sm_axpy_values(h, a, _ptr(delta), _lib.SM_VALUES_OWN, s), "sm_axpy_values")
+        if self._t is not None:
+            check(self._L.sm_axpy_values(self._t._require(), a, _ptr(delta), _lib.SM_VALUES_SOURCE, s),
+                  "sm_axpy_values (T)")
 
     def csr_device(self, stream=None):
         """(row_ptr, col_idx, val): new torch tensors on the matrix's device holding its CSR
         (sm_copy_csr_device; int32, int32, float32), copied on `stream` (None: the current
         torch stream).  ``from_csr(row_ptr, col_idx, new_val, n_cols)`` takes them back, so
-        values can be updated without a host round trip."""
+        values can be updated without a host round trip; a matrix built with
+        ``opts={"updatable": 1}`` takes them in place instead (set_values, axpy_values)."""
         import torch
         inf = self.info()
         dev = torch.device("cuda", self.device)
