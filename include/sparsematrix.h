@@ -125,7 +125,7 @@ typedef struct sm_info {
     int64_t s_rows, s_cols;     /* reference S view: rows_ = k, cols_ = n      */
     int64_t n_rows, n_cols;     /* CSR of B = S^T: n rows, k columns          */
     int64_t nnz;                /* stored entries (explicit zeros included)    */
-    int32_t table_size;         /* codebook size T (0 if built from CSR)       */
+    int32_t table_size;         /* codebook size T (0 if built from CSR values) */
     int32_t has_ref_stream;     /* 1 if the reference encoding is held         */
     int64_t n_entries;          /* reference stream length (nnz + fillers)     */
     int64_t n_panels;           /* reference panels (block_bounds_.size())     */
@@ -168,6 +168,8 @@ typedef struct sm_info {
                                    with several slabs); 0: slab 0 starts from beta*y          */
     int32_t updatable;          /* 1: built with sm_build_opts.updatable (sm_set_values,
                                    sm_axpy_values apply)                                     */
+    int32_t table_updatable;    /* 1: a table matrix built with sm_build_opts.table_updatable
+                                   (sm_set_table, sm_axpy_table apply)                       */
 } sm_info;
 
 /* ---- library ----------------------------------------------------------- */
@@ -294,6 +296,23 @@ typedef struct sm_build_opts {
                                   SM_ERR_NOT_SUPPORTED on such a matrix (the stream would go
                                   stale), so SM_ALGO_NATIVE stays unavailable.  0 (default):
                                   nothing changes -- the same layouts, bytes and digests       */
+    int32_t table_updatable;   /* 1: the table of a table matrix (sm_create_from_csr_ids, and
+                                  sm_create_transpose of one) can be replaced in place
+                                  (sm_set_table, sm_axpy_table).  Every layout that holds values
+                                  then takes its codebook form with the GIVEN ids and the GIVEN
+                                  table -- T entries in the given order, equal entries apart, unused
+                                  entries kept -- so no layout decision reads the values and a new
+                                  table reaches every layout by rewriting its table copy alone.
+                                  AUTO / SM_LAYOUT_BANDS choose among the codebook forms only (cband,
+                                  the sliced ELLs' and the column-chunked ELL's codebook form,
+                                  SM_LAYOUT_SWEEP when forced); where none applies (the sliced ELL
+                                  past 2^24 columns) none is built and the CSR kernels serve.
+                                  SM_ERR_INVALID_ARG with it: SM_LAYOUT_EXACT / BLOCKED / GATHER /
+                                  BAND2 / GCB (plain form only), sell_codebook = 0, hot_cols > 0,
+                                  merge_stage = 1, updatable = 1, and every constructor but the two
+                                  above.  Host builders only, and no sm_build_ref_stream
+                                  (SM_ERR_NOT_SUPPORTED), as for `updatable`.  0 (default): nothing
+                                  changes                                                     */
 } sm_build_opts;
 
 SM_API void sm_build_opts_init(sm_build_opts *opts);
@@ -329,6 +348,31 @@ SM_API sm_status sm_create_from_csr_device_ex(int64_t n_rows, int64_t n_cols, in
  * dense-index source is SM_ERR_NOT_SUPPORTED with it: its values are its codebook. */
 SM_API sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts,
                                      sm_stream stream, sm_matrix **out);
+
+/* A table matrix: the terms of B as (row, col, id) plus one table of T <= 255 floats, the stored
+ * value of term e being table[ids[e]] bit for bit (weight-shared values: quantised centroids).
+ * Host pointers; ids has nnz bytes in CSR order.  table_size must be in [1, 255] when nnz > 0
+ * (SM_ERR_INVALID_ARG otherwise); an id >= table_size is SM_ERR_INVALID_MATRIX.
+ * Without opts->table_updatable the matrix is exactly what sm_create_from_csr_ex builds from the
+ * expanded values (same layouts, digests and products); it only remembers, on the device, the ids
+ * (nnz bytes) and the table, and holds the scratch of sm_sddmm_table (ceil(nnz / 2048) * 256
+ * floats) -- all counted in sm_info.device_bytes.  sm_info.table_size reports T.
+ * The device copy of the table is the authoritative one (sm_set_table / sm_axpy_table are
+ * asynchronous); sm_copy_table_device reads it.  sm_create_transpose of a table matrix gives a
+ * table matrix (the ids travel with the terms, the table is the source's current one) and
+ * honours opts->table_updatable.
+ * Dense-index (CopyForm) matrices are not table matrices: every call of this family returns
+ * SM_ERR_NOT_SUPPORTED on them (INTEGRATION.md shows how to turn an index and its table into
+ * (row_ptr, col_idx, ids, table) for this constructor). */
+SM_API sm_status sm_create_from_csr_ids(int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                        const int32_t *row_ptr, const int32_t *col_idx,
+                                        const uint8_t *ids, const float *table, int32_t table_size,
+                                        int32_t device, const sm_build_opts *opts /* NULL: defaults */,
+                                        sm_matrix **out);
+/* The current table (T floats) / the terms' ids (nnz bytes, CSR order) of a table matrix into
+ * buffers on its device, asynchronous on `stream`.  SM_ERR_NOT_SUPPORTED on any other matrix. */
+SM_API sm_status sm_copy_table_device(const sm_matrix *m, float *d_table, sm_stream stream);
+SM_API sm_status sm_copy_term_ids_device(const sm_matrix *m, uint8_t *d_ids, sm_stream stream);
 
 /* Destroy: sparse-matrix.cc:9-18 (frees host and device storage). */
 SM_API void sm_destroy(sm_matrix *m);
@@ -470,6 +514,54 @@ typedef enum sm_values_order { SM_VALUES_OWN = 0, SM_VALUES_SOURCE = 1 } sm_valu
 SM_API sm_status sm_set_values(sm_matrix *m, const float *d_v, sm_values_order order, sm_stream stream);
 SM_API sm_status sm_axpy_values(sm_matrix *m, float a, const float *d_delta, sm_values_order order,
                                 sm_stream stream);
+
+/* The gradient of the table of a table matrix (sm_create_from_csr_ids with or without
+ * table_updatable, and its transposes; SM_ERR_NOT_SUPPORTED on every other matrix):
+ *   out[t] = alpha * sum over the terms e with id_e = t of <G[r_e, :], X[c_e, :]> + beta * out[t],
+ * t < T -- the sum of sm_sddmm's per-term gradients over the terms that share a table entry,
+ * in one fused pass that writes no nnz-sized array.
+ * Operands: G, X, ldg, ldx, n_rhs as for sm_sddmm (placement only selects the kernel, row offsets
+ *   in 64 bits).  d_out: T floats on the device, any 4-byte alignment, not overlapping G or X.
+ * Summation order (deterministic: no float atomics, the launch geometry a function of nnz and
+ * n_rhs alone; both algorithms, which differ only in d_e):
+ *   1. d_e: the term's dot exactly as sm_sddmm forms s before alpha -- SM_ALGO_PARITY the
+ *      separate-roundings order; AUTO (every other value) the vector kernel's order where that
+ *      kernel takes the placement, else the PARITY order.  The same device code as sm_sddmm.
+ *   2. chunk k holds the terms [2048 k, 2048 (k+1)) in CSR order; p[k][t] = the d_e of the
+ *      chunk's terms with id t in ascending e, added one at a time (round to nearest), from -0.0.
+ *   3. S[t] = p[0][t], p[1][t], ... in ascending k, added one at a time, from -0.0.
+ *   4. out[t] = fl(o + fl(alpha * S[t])), o = out[t] if beta == 1 else fl(beta * out[t]).
+ * Longest rounding path of out[t]: R_t = R_dot + max_k |{e in chunk k : id_e = t}| +
+ *   ceil(nnz / 2048) + 2, R_dot = sm_sddmm's count for the dot itself (n_rhs for PARITY,
+ *   4T + log2 L for the vector kernel), and
+ *     |out[t] - exact| <= R_t * 2^-24 * (|alpha| * sum_e sum_j |G*X| over the id's terms + |beta*out_0|)
+ *   to first order.
+ * alpha == 0 skips the product (G and X may be NULL; only the beta scaling runs).  nnz == 0: the
+ *   finish step alone runs with every S[t] = -0.0.  n_rhs < 1 is SM_ERR_INVALID_ARG.
+ * Streams: asynchronous on `stream`; no allocation and no host synchronisation.  The per-chunk
+ *   partials live in the matrix (allocated at creation): calls on one matrix from any streams
+ *   take turns on the device through an event of their own (they do not serialise with SpMVs);
+ *   into a stream being captured the stream's own order holds, as for the scratch-using SpMVs. */
+SM_API sm_status sm_sddmm_table(const sm_matrix *m, int32_t n_rhs, float alpha, const float *G,
+                                int64_t ldg, const float *X, int64_t ldx, float beta, float *d_out,
+                                sm_algo algo, sm_stream stream);
+
+/* A new table for a table matrix built with sm_build_opts.table_updatable = 1, in place
+ * (SM_ERR_NOT_SUPPORTED otherwise):
+ *   sm_set_table:   table[t] = v[t], bit for bit (NaN payloads, -0.0, denormals);
+ *   sm_axpy_table:  table[t] = fl(table[t] + fl(a * delta[t])) -- two roundings, no fused multiply-add.
+ * Arrays: device pointers to T floats, 4-byte aligned; a null array with T > 0 is
+ *   SM_ERR_INVALID_ARG.  a == 0: SM_OK, nothing launched, `delta` may be NULL.
+ * The calls write the authoritative table, every layout's own table copy (the zero padding past T
+ * of the 256-entry copies included) and the CSR values val[e] = table[ids[e]] (one pass, 1 + 4
+ * bytes per term).  Afterwards the matrix is what sm_create_from_csr_ids builds from the same
+ * pattern and ids, the new table and the same options: the CSR values, sm_equal, sm_layout_digest
+ * and every product of every sm_algo, bit for bit.  A transposed companion takes the same call
+ * with the same array (the table has no term order).
+ * Streams: asynchronous on `stream`, two launches; no allocation, no host synchronisation, no
+ *   scratch, so the calls can be captured.  They WRITE the matrix: ordering as for sm_set_values. */
+SM_API sm_status sm_set_table(sm_matrix *m, const float *d_table, sm_stream stream);
+SM_API sm_status sm_axpy_table(sm_matrix *m, float a, const float *d_delta, sm_stream stream);
 
 /* AddMatMat (sparse-matrix.cc:139-194) on device pointers:
  * C (m x n, ldc) = alpha * A (m x k, lda) * S + beta * C.

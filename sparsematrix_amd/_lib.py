@@ -50,6 +50,8 @@ EXPORTS = (
     "sm_multi_allgather", "sm_multi_set_timing", "sm_multi_last_times", "sm_multi_create_with",
     "sm_debug_seed_handoff", "sm_layout_digest", "sm_sddmm", "sm_copy_csr_device",
     "sm_set_values", "sm_axpy_values",
+    "sm_create_from_csr_ids", "sm_copy_table_device", "sm_copy_term_ids_device", "sm_sddmm_table",
+    "sm_set_table", "sm_axpy_table",
 )
 
 SM_UNIQUE_ID_BYTES = 128
@@ -80,6 +82,7 @@ class SmInfo(C.Structure):
         ("hot_cols", C.c_int32), ("sweep_blocks", C.c_int32),
         ("exact_sell_slices", C.c_int64), ("exact_algo", C.c_int32), ("xband_slab0_cols", C.c_int32),
         ("merge_stage", C.c_int32), ("xband_beta_last", C.c_int32), ("updatable", C.c_int32),
+        ("table_updatable", C.c_int32),
     ]
 
 
@@ -96,7 +99,7 @@ class SmBuildOpts(C.Structure):
         ("sell_sigma", C.c_int64), ("relabel", C.c_int32), ("tile_nnz", C.c_int32),
         ("ccsell", C.c_int32), ("ccsell_chunk_log2", C.c_int32), ("hot_cols", C.c_int32),
         ("exact_sell", C.c_int32), ("band_slab0_permille", C.c_int32), ("merge_stage", C.c_int32),
-        ("host_build", C.c_int32), ("updatable", C.c_int32),
+        ("host_build", C.c_int32), ("updatable", C.c_int32), ("table_updatable", C.c_int32),
     ]
 
 
@@ -161,6 +164,13 @@ def _declare(L):
         "sm_copy_csr_device": ([_vp, _vp, _vp, _vp, _vp], C.c_int),
         "sm_set_values": ([_vp, _vp, C.c_int, _vp], C.c_int),
         "sm_axpy_values": ([_vp, _f32, _vp, C.c_int, _vp], C.c_int),
+        "sm_create_from_csr_ids": ([_i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32,
+                                    C.POINTER(SmBuildOpts), C.POINTER(_vp)], C.c_int),
+        "sm_copy_table_device": ([_vp, _vp, _vp], C.c_int),
+        "sm_copy_term_ids_device": ([_vp, _vp, _vp], C.c_int),
+        "sm_sddmm_table": ([_vp, _i32, _f32, _vp, _i64, _vp, _i64, _f32, _vp, C.c_int, _vp], C.c_int),
+        "sm_set_table": ([_vp, _vp, _vp], C.c_int),
+        "sm_axpy_table": ([_vp, _f32, _vp, _vp], C.c_int),
         "sm_addmatmat": ([_vp, _vp, _i32, _i32, _vp, _i32, _f32, _f32, C.c_int, _vp], C.c_int),
         "sm_addmatmat_host": ([_vp, _vp, _i32, _i32, _vp, _i32, _f32, _f32], C.c_int),
         "sm_beta_scale": ([_vp, _i32, _i32, _i32, _f32, _vp], C.c_int),

@@ -104,6 +104,14 @@ void free_device(sm_matrix *m) {
     m->d_term_ids = nullptr;
     (void)hipFree(m->d_src_term);
     m->d_src_term = nullptr;
+    (void)hipFree(m->d_tab_ids);
+    (void)hipFree(m->d_tab);
+    (void)hipFree(m->d_tab_partials);
+    m->d_tab_ids = nullptr;
+    m->d_tab = m->d_tab_partials = nullptr;
+    if (m->tab_ready) (void)hipEventDestroy(m->tab_ready);
+    m->tab_ready = nullptr;
+    m->tab_recorded = false;
     (void)hipFree(m->plan.d_tiles);
     (void)hipFree(m->plan.d_merge);
     (void)hipFree(m->plan.d_merge_corner);
@@ -194,6 +202,7 @@ BuildOpts resolve_opts(const sm_build_opts *o) {
         r.merge_stage = d.merge_stage;
         r.host_build = d.host_build;
         r.updatable = d.updatable;
+        r.table_updatable = d.table_updatable;
     }
     if (const char *e = dev_env("SM_XBAND")) r.layout = atoi(e) ? SM_LAYOUT_BANDS : SM_LAYOUT_NO_BANDS;
     if (const char *e = dev_env("SM_XBAND_KIND")) {
@@ -222,7 +231,8 @@ BuildOpts resolve_opts(const sm_build_opts *o) {
     return r;
 }
 
-sm_status check_opts(const sm_build_opts *o) {
+// `table_ok`: the constructor builds a table matrix (the only ones that honour table_updatable).
+sm_status check_opts(const sm_build_opts *o, bool table_ok = false) {
     if (!o) return SM_OK;
     if (o->struct_size < (int32_t)(2 * sizeof(int32_t)))
         return fail(SM_ERR_INVALID_ARG, "sm_build_opts.struct_size %d: call sm_build_opts_init",
@@ -254,6 +264,19 @@ sm_status check_opts(const sm_build_opts *o) {
             return fail(SM_ERR_INVALID_ARG, "updatable: layout %d exists only in codebook form", r.layout);
         if (r.hot_cols > 0) return fail(SM_ERR_INVALID_ARG, "updatable: hot_cols exists only in codebook form");
         if (r.merge_stage == 1) return fail(SM_ERR_INVALID_ARG, "updatable: merge_stage exists only in codebook form");
+    }
+    if (r.table_updatable != 0 && r.table_updatable != 1)
+        return fail(SM_ERR_INVALID_ARG, "table_updatable must be 0 or 1");
+    if (r.table_updatable) {   // codebook forms only, from the given ids and table
+        if (!table_ok)
+            return fail(SM_ERR_INVALID_ARG, "table_updatable: only sm_create_from_csr_ids and sm_create_transpose "
+                                            "of a table matrix honour it");
+        if (r.updatable) return fail(SM_ERR_INVALID_ARG, "table_updatable and updatable exclude each other");
+        if ((r.layout >= SM_LAYOUT_EXACT && r.layout <= SM_LAYOUT_BAND2) || r.layout == SM_LAYOUT_GCB)
+            return fail(SM_ERR_INVALID_ARG, "table_updatable: layout %d exists only in plain form", r.layout);
+        if (r.sell_codebook == 0) return fail(SM_ERR_INVALID_ARG, "table_updatable: sell_codebook = 0 asks for the plain form");
+        if (r.hot_cols > 0) return fail(SM_ERR_INVALID_ARG, "table_updatable: hot_cols is not supported");
+        if (r.merge_stage == 1) return fail(SM_ERR_INVALID_ARG, "table_updatable: merge_stage is not supported");
     }
     return SM_OK;
 }
@@ -298,6 +321,8 @@ XbKind xband_kind_setting(const sm_matrix *m) {
     default: break;
     }
     // Updatable matrices take no codebook form: band2's 8-byte entries where cband would serve.
+    // table_updatable ones take only codebook forms: cband wherever a band layout is built.
+    if (m->opts.table_updatable) return kXbCband;
     return m->n_cols >= kGcbCols ? kXbGcb : m->n_cols > kGatherCols ? kXbGather
            : m->opts.updatable ? kXbBand2 : kXbCband;
 }
@@ -361,6 +386,24 @@ bool want_xband(const sm_matrix *m) {
     return xband_cost_ok(m, xband_kind_setting(m));
 }
 
+// The one source of (table, ids) for the codebook forms.  A table_updatable matrix gives its own:
+// the T entries in the given order (equal entries apart, unused ones kept) and the given ids --
+// nothing is derived from the value bits.  Every other matrix derives them from the values
+// (codebook_ids: distinct bit patterns in CSR order; false past 255).  `ids` points into `own`
+// or at the matrix's ids (all nnz terms of the CSR, in its order).
+static bool codebook_source(const sm_matrix *m, const float *val, int64_t nnz, std::vector<float> &table,
+                            std::vector<uint8_t> &own, const uint8_t *&ids) {
+    if (m->opts.table_updatable) {
+        if (!m->build_ids || !m->build_table || nnz != m->nnz) return false;
+        table.assign(m->build_table, m->build_table + m->tab_size);
+        ids = m->build_ids;
+        return true;
+    }
+    if (!codebook_ids(val, nnz, table, own)) return false;
+    ids = own.data();
+    return true;
+}
+
 // Balanced-band layout (band2.cpp, kernels_band2.hip): slabs so there are about
 // kXbTargetTiles tiles of <= 16K rows.  kind cband: 4-byte codebook words when the
 // values take <= 255 distinct bit patterns, else (or kind band2) 8-byte entries.
@@ -382,15 +425,17 @@ static sm_status build_band2(sm_matrix *m, XbandDev &d, int64_t n_rows, int64_t 
     if (slabs > 0) want = std::max(1, std::min(16, slabs));
     std::vector<float> table;
     std::vector<uint8_t> ids;
+    const uint8_t *idp = nullptr;
     const bool upd = m->opts.updatable != 0;   // no layout decision reads the values
-    const bool cb = kind == kXbCband && !upd && codebook_ids(val, nnz, table, ids);
+    const bool cb = kind == kXbCband && !upd && codebook_source(m, val, nnz, table, ids, idp);
+    if (m->opts.table_updatable && !cb) return SM_OK;   // codebook form or none
     Band2Host bh;
     B2Geom g = dma3 ? (cb ? kB2Dma3Cb : kB2Dma3B2) : kB2Wide;
     // Bands are fixed slots of g.chunks() * 64 entries: where a slab's density leaves
     // them mostly dummies (wide or very sparse matrices), the padding would cost more HBM
     // bytes than the layout saves -- decline unless forced (SM_LAYOUT_BAND2 / CBAND).
     auto fits = [&](const B2Geom &gg) {
-        if (!band2_build(rp, col, val, n_rows, n_cols, want, bh, cb ? ids.data() : nullptr, gg, slab0_permille, upd))
+        if (!band2_build(rp, col, val, n_rows, n_cols, want, bh, cb ? idp : nullptr, gg, slab0_permille, upd))
             return false;
         return forced || bh.n_bands == 0 ||
                (double)bh.real_terms >= 0.7 * (double)bh.n_bands * gg.chunks() * 64;
@@ -524,7 +569,7 @@ sm_status upload_xband(sm_matrix *m, const int32_t *rp, const int32_t *col, cons
     if (kind == kXbGcb) return upload_gcb(m, rp, col, val);
     if (kind == kXbBand2 || kind == kXbCband) {
         const sm_status st = upload_band2(m, rp, col, val, kind);
-        if (st == SM_OK && m->plan.xb.n_blocks == 0 && !kind_forced(m))
+        if (st == SM_OK && m->plan.xb.n_blocks == 0 && !kind_forced(m) && !m->opts.table_updatable)
             return upload_xband(m, rp, col, val, kXbBlocked);   // declined: blocked kind
         return st;
     }
@@ -717,11 +762,13 @@ sm_status upload_sell(sm_matrix *m, const int32_t *rp, const int32_t *col, const
     std::vector<float> table;
     std::vector<uint8_t> ids;
     const bool upd = m->opts.updatable != 0;   // the plain form: no decision reads the values
+    const uint8_t *idp = nullptr;
     const bool cb = m->opts.sell_codebook != 0 && !upd && m->n_cols <= ((int64_t)1 << kSellCbColBits) &&
-                    codebook_ids(val, nnz, table, ids);
+                    codebook_source(m, val, nnz, table, ids, idp);
+    if (m->opts.table_updatable && !cb) return SM_OK;   // codebook form or none: the stream kernel serves
     if (!cb) std::vector<uint8_t>().swap(ids);
     SellHost sh;
-    sell_build(rp, c, val, m->n_rows, max_len, sh, sigma, streams, cb ? ids.data() : nullptr, upd);
+    sell_build(rp, c, val, m->n_rows, max_len, sh, sigma, streams, cb ? idp : nullptr, upd);
     std::vector<int32_t>().swap(rcol);
     std::vector<uint8_t>().swap(ids);
     if (sh.n_slices == 0) return SM_OK;
@@ -816,9 +863,10 @@ bool want_sweep(const sm_matrix *m) {
 sm_status upload_sweep(sm_matrix *m, const int32_t *rp, const int32_t *col, const float *val) {
     std::vector<float> table;
     std::vector<uint8_t> ids;
-    if (!codebook_ids(val, m->nnz, table, ids) || table.size() > 255) return SM_OK;   // not applicable
+    const uint8_t *idp = nullptr;
+    if (!codebook_source(m, val, m->nnz, table, ids, idp) || table.size() > 255) return SM_OK;   // not applicable
     SweepHost h;
-    if (!sweep_build(rp, col, ids.data(), m->n_rows, h)) return SM_OK;
+    if (!sweep_build(rp, col, idp, m->n_rows, h)) return SM_OK;
     std::vector<uint8_t>().swap(ids);
     SweepDev &d = m->plan.sw;
     SM_TRY_HIP(dev_alloc(&d.d_block_chunk, (int64_t)h.block_chunk.size(), m->device_bytes));
@@ -849,13 +897,15 @@ sm_status upload_ccsell(sm_matrix *m, const int32_t *rp, const int32_t *col, con
     std::vector<float> table;
     std::vector<uint8_t> ids;
     const bool upd = m->opts.updatable != 0;   // the plain form: no decision reads the values
-    const bool cb = m->opts.sell_codebook != 0 && !upd && cl <= 24 && codebook_ids(val, m->nnz, table, ids);
+    const uint8_t *idp = nullptr;
+    const bool cb = m->opts.sell_codebook != 0 && !upd && cl <= 24 && codebook_source(m, val, m->nnz, table, ids, idp);
+    if (m->opts.table_updatable && !cb) return SM_OK;   // codebook form or none
     if (!cb) std::vector<uint8_t>().swap(ids);
     CcsellHost h;
     // SM_CCSELL_ROWORDER (development A/B): units in row order instead of by length.
     const char *ro = dev_env("SM_CCSELL_ROWORDER");
     const bool by_length = !(ro && atoi(ro) == 1);
-    if (!ccsell_build(rp, col, val, cb ? ids.data() : nullptr, m->n_rows, m->n_cols, cl, h, by_length, upd))
+    if (!ccsell_build(rp, col, val, cb ? idp : nullptr, m->n_rows, m->n_cols, cl, h, by_length, upd))
         return SM_OK;   // not applicable: the sliced ELL serves the matrix
     std::vector<uint8_t>().swap(ids);
     if (h.n_slices == 0) return SM_OK;
@@ -1135,6 +1185,31 @@ sm_status finish_from_host_csr(sm_matrix *m, const int32_t *rp, const int32_t *c
     if (st2 == SM_OK && want_merge_stage(m)) st2 = upload_merge_stage(m, rp, col, val);
     if (st2 == SM_OK && want_exact_sell(m)) st2 = upload_exact_sell(m, rp, col, val);
     return st2;
+}
+
+// The device side of a table matrix (sm_internal.h): the ids (filled by the caller), the
+// authoritative table of 256 floats (zero past T; `table` a host pointer, or null when the caller
+// copies it on the device) and sm_sddmm_table's partials, all counted in device_bytes.
+sm_status alloc_table(sm_matrix *m, const float *table, int32_t table_size) {
+    m->is_table = true;
+    m->tab_size = table_size;
+    m->tab_chunks = (m->nnz + kSddmmChunk - 1) / kSddmmChunk;
+    SM_TRY_HIP(dev_alloc(&m->d_tab_ids, m->nnz, m->device_bytes));
+    SM_TRY_HIP(dev_alloc(&m->d_tab, 256, m->device_bytes));
+    SM_TRY_HIP(dev_alloc(&m->d_tab_partials, m->tab_chunks * kTablePartialStride, m->device_bytes));
+    SM_TRY_HIP(hipMemset(m->d_tab, 0, 256 * sizeof(float)));
+    if (table && table_size > 0)
+        SM_TRY_HIP(hipMemcpy(m->d_tab, table, (size_t)table_size * 4, hipMemcpyHostToDevice));
+    return SM_OK;
+}
+
+const char *kNotTable = "not a table matrix (sm_create_from_csr_ids)";
+const char *kIndexHint = "a dense-index matrix is not a table matrix: build it with sm_create_from_csr_ids from "
+                         "(row_ptr, col_idx, ids, table), see INTEGRATION.md";
+sm_status need_table(const sm_matrix *m, const char *what) {
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (!m->is_table) return fail(SM_ERR_NOT_SUPPORTED, "%s: %s", what, m->from_index ? kIndexHint : kNotTable);
+    return SM_OK;
 }
 
 std::unique_ptr<sm_matrix> new_matrix(int32_t device, const sm_build_opts *opts = nullptr) {
@@ -1469,6 +1544,62 @@ sm_status sm_create_from_csr_ex(int64_t n_rows, int64_t n_cols, int64_t nnz,
     return SM_OK;
 }
 
+sm_status sm_create_from_csr_ids(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t *row_ptr,
+                                 const int32_t *col_idx, const uint8_t *ids, const float *table,
+                                 int32_t table_size, int32_t device, const sm_build_opts *opts, sm_matrix **out) {
+    if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    sm_status st = check_opts(opts, true);
+    if (st != SM_OK) return st;
+    st = check_sizes(n_rows, n_cols, nnz);
+    if (st != SM_OK) return st;
+    if (!row_ptr || (nnz > 0 && (!col_idx || !ids))) return fail(SM_ERR_INVALID_ARG, "null CSR array");
+    if (table_size < 0 || table_size > 255 || (nnz > 0 && table_size < 1))
+        return fail(SM_ERR_INVALID_ARG, "table_size %d not in [1, 255]", table_size);
+    if (table_size > 0 && !table) return fail(SM_ERR_INVALID_ARG, "null table");
+    if (row_ptr[0] != 0 || row_ptr[n_rows] != nnz)
+        return fail(SM_ERR_INVALID_MATRIX, "row_ptr[0] must be 0 and row_ptr[n] == nnz");
+    for (int64_t r = 0; r < n_rows; r++)
+        if (row_ptr[r + 1] < row_ptr[r])
+            return fail(SM_ERR_INVALID_MATRIX, "row_ptr decreases at row %lld", (long long)r);
+    for (int64_t e = 0; e < nnz; e++) {
+        if (col_idx[e] < 0 || col_idx[e] >= n_cols)
+            return fail(SM_ERR_INVALID_MATRIX, "col_idx[%lld] = %d out of range", (long long)e, col_idx[e]);
+        if (ids[e] >= table_size)
+            return fail(SM_ERR_INVALID_MATRIX, "ids[%lld] = %d >= table_size %d", (long long)e, (int)ids[e], table_size);
+    }
+    st = check_device(device);
+    if (st != SM_OK) return st;
+    DeviceGuard g(device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    std::vector<float> val((size_t)nnz);   // the stored values: table[ids[e]], bit for bit
+    for (int64_t e = 0; e < nnz; e++) memcpy(&val[(size_t)e], &table[ids[e]], 4);
+    auto m = new_matrix(device, opts);
+    m->n_rows = n_rows;
+    m->n_cols = n_cols;
+    m->nnz = nnz;
+    m->s_rows = n_cols;
+    m->s_cols = n_rows;
+    st = alloc_table(m.get(), table, table_size);
+    if (st == SM_OK && nnz) {
+        const hipError_t e = hipMemcpy(m->d_tab_ids, ids, (size_t)nnz, hipMemcpyHostToDevice);
+        if (e != hipSuccess) st = hip_fail(e, "upload term ids");
+    }
+    if (st == SM_OK) {
+        m->build_ids = ids;
+        m->build_table = table;
+        st = finish_from_host_csr(m.get(), row_ptr, col_idx, val.data());
+        m->build_ids = nullptr;
+        m->build_table = nullptr;
+    }
+    if (st != SM_OK) {
+        free_device(m.get());
+        return st;
+    }
+    *out = m.release();
+    return SM_OK;
+}
+
 sm_status sm_create_from_csr_device(int64_t n_rows, int64_t n_cols, int64_t nnz,
                                     const int32_t *d_row_ptr, const int32_t *d_col_idx,
                                     const float *d_val, int32_t device, sm_stream stream,
@@ -1508,7 +1639,8 @@ static sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_
     // host).  R-MAT 24: the host path took 5.4 s.
     bool dev_done = false;
     // An updatable matrix is built as host_build = 1: only the host builders emit the slot -> term maps.
-    const bool dev_ok = st == SM_OK && m->opts.host_build == 0 && m->opts.updatable == 0 && !want_sweep(m) &&
+    const bool dev_ok = st == SM_OK && m->opts.host_build == 0 && m->opts.updatable == 0 && m->opts.table_updatable == 0 &&
+                        !want_sweep(m) &&
                         m->opts.hot_cols <= 0 &&
                         m->opts.sell_sigma == 0 && m->opts.sell_streams <= 1 && m->opts.exact_sell != 1;
     // The gathered chunk bands on the device (builddev_gcb.hip; config 5: 15 s on the host path).
@@ -1673,7 +1805,7 @@ sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts, s
     if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
     *out = nullptr;
     if (!src) return fail(SM_ERR_INVALID_ARG, "null matrix");
-    sm_status st = check_opts(opts);
+    sm_status st = check_opts(opts, src->is_table);
     if (st != SM_OK) return st;
     st = check_sizes(src->n_cols, src->n_rows, src->nnz);
     if (st != SM_OK) return st;
@@ -1724,7 +1856,32 @@ sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts, s
             if (e != hipSuccess) st = hip_fail(e, "sm_create_transpose (source terms)");
         }
     }
+    // A table matrix hands on its ids (through the same sort as the terms) and its current table;
+    // a table_updatable result also needs both on the host for the layout builders.
+    std::vector<uint8_t> h_ids;
+    std::vector<float> h_tab;
+    if (st == SM_OK && src->is_table) {
+        st = alloc_table(m.get(), nullptr, src->tab_size);
+        hipError_t e = hipSuccess;
+        if (st == SM_OK) e = hipMemcpyAsync(m->d_tab, src->d_tab, 256 * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (st == SM_OK && e == hipSuccess && m->nnz > 0)
+            e = transpose_ids_device(src->d_row_ptr, src->d_col, src->d_tab_ids, src->n_rows, src->n_cols, src->nnz,
+                                     m->d_tab_ids, s);
+        if (st == SM_OK && e == hipSuccess && m->opts.table_updatable) {
+            h_ids.resize((size_t)m->nnz);
+            h_tab.resize(256);
+            e = hipStreamSynchronize(s);
+            if (e == hipSuccess && m->nnz > 0)
+                e = hipMemcpy(h_ids.data(), m->d_tab_ids, (size_t)m->nnz, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(h_tab.data(), m->d_tab, 256 * sizeof(float), hipMemcpyDeviceToHost);
+            m->build_ids = h_ids.data();
+            m->build_table = h_tab.data();
+        }
+        if (st == SM_OK && e != hipSuccess) st = hip_fail(e, "sm_create_transpose (table)");
+    }
     if (st == SM_OK) st = finish_from_device_csr(m.get(), s, true);
+    m->build_ids = nullptr;
+    m->build_table = nullptr;
     if (st != SM_OK) {
         free_device(m.get());
         (void)hipGetLastError();   // a failed allocation leaves no sticky error behind
@@ -1764,7 +1921,7 @@ sm_status sm_get_info_ex(const sm_matrix *m, sm_info *out, size_t info_bytes) {
     info->n_rows = m->n_rows;
     info->n_cols = m->n_cols;
     info->nnz = m->nnz;
-    info->table_size = m->table_size;
+    info->table_size = m->is_table ? m->tab_size : m->table_size;
     info->has_ref_stream = m->has_ref ? 1 : 0;
     info->n_entries = (int64_t)m->pos.size();
     info->n_panels = (int64_t)m->panel_col_off.size();
@@ -1788,6 +1945,7 @@ sm_status sm_get_info_ex(const sm_matrix *m, sm_info *out, size_t info_bytes) {
                             (m->plan.xb.kind == kXbBand2 || m->plan.xb.kind == kXbCband);
     info->device_bytes = m->device_bytes;
     info->updatable = m->opts.updatable ? 1 : 0;
+    info->table_updatable = m->opts.table_updatable ? 1 : 0;
     info->col_relabel = m->plan.n_relabel > 0 ? 1 : 0;
     info->sell_slices = m->plan.sell.n_slices;
     info->sell_codebook = m->plan.sell.d_table != nullptr || m->plan.cc.d_table != nullptr;
@@ -1890,6 +2048,8 @@ sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t table_si
     if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
     if (m->opts.updatable)
         return fail(SM_ERR_NOT_SUPPORTED, "updatable matrix: the stream would go stale with the next update");
+    if (m->opts.table_updatable)
+        return fail(SM_ERR_NOT_SUPPORTED, "table_updatable matrix: the stream would go stale with the next update");
     if (m->has_ref) return SM_OK;
     if (table && (table_size < 0 || table_size > 255))
         return fail(SM_ERR_INVALID_ARG, "table_size %d not in [0, 255]", table_size);
@@ -2246,6 +2406,103 @@ sm_status sm_set_values(sm_matrix *m, const float *d_v, sm_values_order order, s
 
 sm_status sm_axpy_values(sm_matrix *m, float a, const float *d_delta, sm_values_order order, sm_stream stream) {
     return update_values(m, true, a, d_delta, order, stream, "sm_axpy_values");
+}
+
+sm_status sm_copy_table_device(const sm_matrix *m, float *d_table, sm_stream stream) {
+    if (const sm_status st = need_table(m, "sm_copy_table_device")) return st;
+    if (m->tab_size == 0) return SM_OK;
+    if (!d_table) return fail(SM_ERR_INVALID_ARG, "sm_copy_table_device: null array");
+    DeviceGuard g(m->device);
+    SM_TRY_HIP(hipMemcpyAsync(d_table, m->d_tab, (size_t)m->tab_size * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SM_OK;
+}
+
+sm_status sm_copy_term_ids_device(const sm_matrix *m, uint8_t *d_ids, sm_stream stream) {
+    if (const sm_status st = need_table(m, "sm_copy_term_ids_device")) return st;
+    if (m->nnz == 0) return SM_OK;
+    if (!d_ids) return fail(SM_ERR_INVALID_ARG, "sm_copy_term_ids_device: null array");
+    DeviceGuard g(m->device);
+    SM_TRY_HIP(hipMemcpyAsync(d_ids, m->d_tab_ids, (size_t)m->nnz, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SM_OK;
+}
+
+sm_status sm_sddmm_table(const sm_matrix *m, int32_t n_rhs, float alpha, const float *G, int64_t ldg,
+                         const float *X, int64_t ldx, float beta, float *d_out, sm_algo algo, sm_stream stream) {
+    if (n_rhs < 1) return fail(SM_ERR_INVALID_ARG, "n_rhs < 1");   // before the matrix is looked at
+    if (const sm_status st = need_table(m, "sm_sddmm_table")) return st;
+    if (ldg < n_rhs || ldx < n_rhs) return fail(SM_ERR_INVALID_ARG, "ldg/ldx < n_rhs");
+    if (algo < SM_ALGO_AUTO || algo > SM_ALGO_MERGE) return fail(SM_ERR_INVALID_ARG, "unknown algo %d", (int)algo);
+    const int32_t T = m->tab_size;
+    if (T == 0) return SM_OK;
+    if (!d_out || (alpha != 0.0f && m->nnz > 0 && (!G || !X))) return fail(SM_ERR_INVALID_ARG, "null G/X/out");
+    DeviceGuard g(m->device);
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e;
+    if (alpha == 0.0f) {
+        e = beta != 1.0f ? launch_beta(d_out, 1, T, T, beta, s) : hipSuccess;
+        return e == hipSuccess ? SM_OK : hip_fail(e, "sm_sddmm_table beta");
+    }
+    const int32_t nnz = (int32_t)m->nnz;
+    const bool panel = algo != SM_ALGO_PARITY && nnz > 0 && sddmm_panel_ok(m->n_rows, m->n_cols, n_rhs, G, ldg, X, ldx);
+    {   // the partials belong to the matrix: calls take turns on the device (as with_scratch)
+        std::lock_guard<std::mutex> lk(m->tab_mu);
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
+        const bool ordered = cs == hipStreamCaptureStatusNone;
+        e = hipSuccess;
+        if (ordered && !m->tab_ready) e = hipEventCreateWithFlags(&m->tab_ready, hipEventDisableTiming);
+        if (ordered && e == hipSuccess && m->tab_recorded) e = hipStreamWaitEvent(s, m->tab_ready, 0);
+        if (e != hipSuccess) return hip_fail(e, "sm_sddmm_table scratch ordering");
+        e = launch_sddmm_table(panel, (int32_t)m->n_rows, (int32_t)m->n_cols, nnz, n_rhs, m->d_row_ptr, m->d_col,
+                               m->d_tab_ids, T, G, ldg, X, ldx, m->d_tab_partials, s);
+        if (e == hipSuccess) e = launch_table_finish(m->tab_chunks, T, m->d_tab_partials, d_out, alpha, beta, s);
+        if (ordered) {   // whatever was queued uses the partials
+            const hipError_t er = hipEventRecord(m->tab_ready, s);
+            if (er == hipSuccess) m->tab_recorded = true;
+            if (e == hipSuccess) e = er;
+        }
+    }
+    e = after_launch(e, s, "sm_sddmm_table");
+    return e == hipSuccess ? SM_OK : hip_fail(e, "sm_sddmm_table launch");
+}
+
+// The table step (the authoritative table and every layout's copy), then the CSR values
+// (kernels_values.hip): launches only, so the call can be captured.
+static sm_status update_table(sm_matrix *m, bool axpy, float a, const float *d_in, sm_stream stream,
+                              const char *what) {
+    if (const sm_status st = need_table(m, what)) return st;
+    if (!m->opts.table_updatable)
+        return fail(SM_ERR_NOT_SUPPORTED, "%s: the matrix was not built with sm_build_opts.table_updatable", what);
+    if (m->tab_size == 0 || (axpy && a == 0.0f)) return SM_OK;
+    if (!d_in) return fail(SM_ERR_INVALID_ARG, "%s: null array", what);
+    DeviceGuard g(m->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    const Plan &p = m->plan;
+    TableDst dst{};
+    auto add = [&](float *tab, int32_t n) {
+        if (!tab) return;
+        dst.p[dst.count] = tab;
+        dst.n[dst.count++] = n;
+    };
+    if (p.xb.n_blocks > 0) add(p.xb.d_table, 256);
+    if (p.sell.n_slices > 0) add(p.sell.d_table, p.sell.table_size);
+    if (p.xsell.n_slices > 0) add(p.xsell.d_table, p.xsell.table_size);
+    if (p.cc.n_slices > 0) add(p.cc.d_table, 256);
+    if (p.sw.n_blocks > 0) add(p.sw.d_table, 256);
+    hipError_t e = launch_table_step(m->tab_size, axpy, a, d_in, m->d_tab, dst, s);
+    if (e == hipSuccess) e = launch_values_from_table(m->nnz, m->d_tab_ids, m->d_tab, m->d_val, s);
+    e = after_launch(e, s, what);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return SM_OK;
+}
+
+sm_status sm_set_table(sm_matrix *m, const float *d_table, sm_stream stream) {
+    return update_table(m, false, 0.0f, d_table, stream, "sm_set_table");
+}
+
+sm_status sm_axpy_table(sm_matrix *m, float a, const float *d_delta, sm_stream stream) {
+    return update_table(m, true, a, d_delta, stream, "sm_axpy_table");
 }
 
 sm_status sm_copy_csr_device(const sm_matrix *m, int32_t *d_row_ptr, int32_t *d_col_idx, float *d_val,

@@ -20,6 +20,11 @@
 // (band2, gcb): a lane's 16-byte entry is {word, word, value, value}; one lane takes one entry,
 // an 8-byte map load and one 8-byte store to words 2-3 (4 bytes when only one is a term).
 // All offsets are 64-bit.  No LDS, no atomics, no scratch.
+//
+// Table matrices (sm_set_table, sm_axpy_table; DESIGN.md "Table matrices") need no maps: their
+// layouts hold ids, so an update is the table step -- one workgroup writes the new entries into
+// the authoritative table and every layout's table copy -- and one CSR pass val[e] = tab[ids[e]]
+// (1 + 4 bytes per term, the table staged in LDS) for the kernels that read the CSR values.
 #include <algorithm>
 
 #include "sm_internal.h"
@@ -123,7 +128,62 @@ __global__ __launch_bounds__(kValThreads) void refresh_entry_kernel(int64_t n_en
     }
 }
 
+// Table matrices (sm_set_table, sm_axpy_table).  One workgroup: thread t < table_size forms the
+// new entry and stores it into the authoritative table and every layout's copy; the copies'
+// entries past table_size (the 256-entry ones) are stored as 0, what the builders put there.
+template <bool AXPY>
+__global__ __launch_bounds__(kValThreads) void table_step_kernel(int32_t table_size, float a,
+                                                                 const float *__restrict__ in, float *tab,
+                                                                 TableDst dst) {
+    const int32_t t = threadIdx.x;
+    float v = 0.0f;
+    if (t < table_size) {
+        v = step(tab[t], a, in[t], AXPY);
+        tab[t] = v;
+    }
+    for (int32_t i = 0; i < dst.count; ++i)
+        if (t < dst.n[i]) dst.p[i][t] = v;
+}
+
+// val[e] = tab[ids[e]]: the table staged in LDS, four terms per lane and step (one 4-byte id
+// load, one 16-byte store; ids and val are device allocations, so both are aligned), the tail
+// one at a time.  Only val[0, nnz) is written.
+__global__ __launch_bounds__(kValThreads) void values_from_table_kernel(int64_t nnz, const uint8_t *__restrict__ ids,
+                                                                        const float *__restrict__ tab,
+                                                                        float *__restrict__ val) {
+    __shared__ float stab[256];
+    stab[threadIdx.x] = tab[threadIdx.x];   // the authoritative table holds 256 floats
+    __syncthreads();
+    const int64_t n4 = nnz >> 2;
+    const uint32_t *id4 = reinterpret_cast<const uint32_t *>(ids);
+    float4 *val4 = reinterpret_cast<float4 *>(val);
+    VAL_LOOP(i, n4) {
+        const uint32_t w = id4[i];
+        val4[i] = make_float4(stab[w & 255u], stab[(w >> 8) & 255u], stab[(w >> 16) & 255u], stab[w >> 24]);
+    }
+    VAL_LOOP(j, nnz - (n4 << 2)) {
+        const int64_t e = (n4 << 2) + j;
+        val[e] = stab[ids[e]];
+    }
+}
+
 }  // namespace
+
+hipError_t launch_table_step(int32_t table_size, bool axpy, float a, const float *in, float *tab,
+                             const TableDst &dst, hipStream_t s) {
+    if (table_size <= 0) return hipSuccess;
+    static_assert(kValThreads == 256, "one thread per table slot");
+    if (axpy) hipLaunchKernelGGL(table_step_kernel<true>, dim3(1), dim3(kValThreads), 0, s, table_size, a, in, tab, dst);
+    else hipLaunchKernelGGL(table_step_kernel<false>, dim3(1), dim3(kValThreads), 0, s, table_size, a, in, tab, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_values_from_table(int64_t nnz, const uint8_t *ids, const float *tab, float *val, hipStream_t s) {
+    if (nnz <= 0) return hipSuccess;
+    hipLaunchKernelGGL(values_from_table_kernel, dim3(val_grid((nnz + 3) >> 2)), dim3(kValThreads), 0, s, nnz, ids,
+                       tab, val);
+    return hipGetLastError();
+}
 
 hipError_t launch_values_csr(int64_t nnz, bool axpy, float a, const float *in, const int32_t *src, float *val,
                              hipStream_t s) {

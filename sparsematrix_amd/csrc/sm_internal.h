@@ -58,6 +58,7 @@ struct BuildOpts {
     int32_t merge_stage = 0;           // sm_build_opts.merge_stage
     int32_t host_build = 0;            // sm_build_opts.host_build
     int32_t updatable = 0;             // sm_build_opts.updatable
+    int32_t table_updatable = 0;       // sm_build_opts.table_updatable
 };
 
 // Row tile: rows [r0, r1) whose terms fit one LDS tile.  flags bit0: the tile
@@ -308,6 +309,18 @@ bool sddmm_panel_ok(int64_t n_rows, int64_t n_cols, int32_t n_rhs, const float *
 hipError_t launch_sddmm_panel(int32_t n_rows, int32_t n_cols, int32_t nnz, int32_t n_rhs, const int32_t *rp,
                               const int32_t *col, const float *G, int64_t ldg, const float *X, int64_t ldx,
                               float *out, float alpha, float beta, hipStream_t s);
+// sm_sddmm_table (kernels_sddmm.hip): the same dots, binned by the terms' ids instead of stored.
+// One workgroup per chunk of kSddmmChunk terms forms its terms' dots (`panel`: the vector kernel's
+// order, only where sddmm_panel_ok holds; else the PARITY order) into LDS and writes
+// partials[k * kTablePartialStride + t], t < table_size; launch_table_finish then adds the chunks'
+// partials in ascending k and applies alpha / beta.  No atomics; no nnz-sized array.
+constexpr int kTablePartialStride = 256;
+hipError_t launch_sddmm_table(bool panel, int32_t n_rows, int32_t n_cols, int32_t nnz, int32_t n_rhs,
+                              const int32_t *rp, const int32_t *col, const uint8_t *ids, int32_t table_size,
+                              const float *G, int64_t ldg, const float *X, int64_t ldx, float *partials,
+                              hipStream_t s);
+hipError_t launch_table_finish(int64_t n_chunks, int32_t table_size, const float *partials, float *out,
+                               float alpha, float beta, hipStream_t s);
 hipError_t launch_beta(float *c, int32_t m, int32_t n, int64_t ldc, float beta, hipStream_t s);
 hipError_t launch_transpose(const float *a, int32_t m, int32_t n, int64_t lda, float *sa,
                             int64_t ldsa, hipStream_t s);
@@ -365,6 +378,18 @@ hipError_t launch_values_csr(int64_t nnz, bool axpy, float a, const float *in, c
                              hipStream_t s);
 hipError_t launch_refresh_plain(int64_t n_slots, const int32_t *map, const float *val, float *slot, hipStream_t s);
 hipError_t launch_refresh_entry(int64_t n_ent, const int32_t *map, const float *val, uint32_t *ent, hipStream_t s);
+// In-place table updates (kernels_values.hip).  Table step: one workgroup computes the new entries
+// (set: in[t]; axpy: fl(tab[t] + fl(a * in[t]))), t < table_size, and stores them into the
+// authoritative table and every layout's copy (dst[i], n[i] entries: zero past table_size).
+// CSR step: val[e] = tab[ids[e]], one pass of 1 + 4 bytes per term.
+struct TableDst {
+    float *p[8];
+    int32_t n[8];
+    int32_t count;
+};
+hipError_t launch_table_step(int32_t table_size, bool axpy, float a, const float *in, float *tab,
+                             const TableDst &dst, hipStream_t s);
+hipError_t launch_values_from_table(int64_t nnz, const uint8_t *ids, const float *tab, float *val, hipStream_t s);
 hipError_t launch_validate(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t *rp,
                            const int32_t *col, int32_t *d_flag, hipStream_t s);
 // Dense decode: out is zeroed by the caller.  b_layout: out[row*stride+col]
@@ -407,6 +432,24 @@ struct sm_matrix {
     // (nnz entries), so values given in the source's order reach it (SM_VALUES_SOURCE).
     int32_t *d_src_term = nullptr;
     bool has_src_term = false;   // (also true with nnz == 0, where there is nothing to allocate)
+    // Table matrix (sm_create_from_csr_ids and its transposes): the terms' ids (nnz bytes, CSR
+    // order) and the authoritative table (256 floats, zero past tab_size) on the device, and the
+    // per-chunk partials of sm_sddmm_table (tab_chunks * kTablePartialStride floats) with the
+    // event that makes its calls take turns (as scratch_ready does for the SpMVs).  These fields
+    // are apart from table / d_term_ids above, whose invariants belong to the dense-index path.
+    bool is_table = false;
+    int32_t tab_size = 0;
+    uint8_t *d_tab_ids = nullptr;
+    float *d_tab = nullptr;
+    float *d_tab_partials = nullptr;
+    int64_t tab_chunks = 0;
+    mutable std::mutex tab_mu;
+    mutable hipEvent_t tab_ready = nullptr;
+    mutable bool tab_recorded = false;
+    // While a table_updatable matrix is being built: the host copies the layout builders take
+    // their ids and table from (owned by the constructor; null afterwards).
+    const uint8_t *build_ids = nullptr;
+    const float *build_table = nullptr;
     std::vector<uint8_t> pos, val;
     std::vector<int32_t> panel_row_off, panel_col_off;
     std::vector<int64_t> panel_begin, panel_end;

@@ -210,6 +210,32 @@ class SparseMatrix:
         self._h = h
         return self
 
+    @classmethod
+    def from_csr_ids(cls, row_ptr, col_idx, ids, table, n_cols: int, device: int = 0,
+                     opts: Optional[dict] = None) -> "SparseMatrix":
+        """A table matrix (sm_create_from_csr_ids): the terms of B (n_rows x n_cols) as
+        (row, col, id) plus one table of T <= 255 float32 values; term e stores table[ids[e]].
+        Host (numpy) arrays; `ids`: nnz uint8 in CSR order, each < T.  Without options the matrix
+        is what from_csr builds from ``table[ids]``; it also remembers ids and table, so
+        sddmm_table applies.  ``opts={"table_updatable": 1}`` builds every layout in its codebook
+        form from the given ids and table, so set_table / axpy_table replace the table in place."""
+        self = cls(device=device)
+        rp = np.ascontiguousarray(row_ptr, np.int32)
+        ci = np.ascontiguousarray(col_idx, np.int32)
+        idv = np.ascontiguousarray(ids, np.uint8).reshape(-1)
+        tb = np.ascontiguousarray(table, np.float32).reshape(-1)
+        if idv.size != ci.size:
+            raise ValueError(f"ids has {idv.size} elements, col_idx {ci.size}")
+        if tb.size > 255 or (ci.size > 0 and tb.size < 1):
+            raise ValueError(f"table must hold 1..255 values, got {tb.size}")
+        h = C.c_void_p()
+        o = _lib.build_opts(**(opts or {}))
+        st = self._L.sm_create_from_csr_ids(int(rp.shape[0]) - 1, n_cols, int(ci.size), _ptr(rp), _ptr(ci),
+                                            _ptr(idv), _ptr(tb), int(tb.size), device, C.byref(o), C.byref(h))
+        check(st, "from_csr_ids")
+        self._h = h
+        return self
+
     # ---- the transposed matrix ---------------------------------------------
     def transposed(self, opts: Optional[dict] = None, stream=None) -> "SparseMatrix":
         """A new, independent SparseMatrix holding B^T (sm_create_transpose): transposed on the
@@ -222,6 +248,8 @@ class SparseMatrix:
         t = SparseMatrix(device=self.device)
         if self._updatable():   # the companion of an updatable matrix follows its updates
             opts = dict(opts or {}, updatable=1)
+        if self._table_updatable():
+            opts = dict(opts or {}, table_updatable=1)
         o = _lib.build_opts(**(opts or {}))
         h = C.c_void_p()
         st = self._L.sm_create_transpose(h0, C.byref(o), _stream_of(self, stream), C.byref(h))
@@ -438,8 +466,19 @@ class SparseMatrix:
             inf = self.info()
             self._nnz_cache = inf["nnz"]
             self._upd_cache = bool(inf["updatable"])
+            self._tupd_cache = bool(inf["table_updatable"])
+            self._tsize_cache = inf["table_size"]
             self._nnz_h = h
         return self._nnz_cache
+
+    def _table_updatable(self) -> bool:
+        """Built with opts table_updatable=1 (cached per handle like _nnz)."""
+        self._nnz()
+        return self._tupd_cache
+
+    def _table_size(self) -> int:
+        self._nnz()
+        return self._tsize_cache
 
     def _updatable(self) -> bool:
         """Built with opts updatable=1 (cached per handle like _nnz)."""
@@ -486,6 +525,96 @@ class SparseMatrix:
         if self._t is not None:
             check(self._L.sm_axpy_values(self._t._require(), a, _ptr(delta), _lib.SM_VALUES_SOURCE, s),
                   "sm_axpy_values (T)")
+
+    # ---- table matrices (from_csr_ids): table gradient and in-place table updates ----------
+    def table_device(self, stream=None):
+        """The current table of a table matrix as a new float32 tensor of T elements on its
+        device (sm_copy_table_device), copied on `stream` (None: the current torch stream)."""
+        import torch
+        h = self._require()
+        t = torch.empty(self._table_size(), dtype=torch.float32, device=torch.device("cuda", self.device))
+        check(self._L.sm_copy_table_device(h, _ptr(t) if t.numel() else 0, _stream_of(t, stream)),
+              "sm_copy_table_device")
+        return t
+
+    def term_ids_device(self, stream=None):
+        """The terms' ids of a table matrix in CSR order, a new uint8 tensor of nnz elements on
+        its device (sm_copy_term_ids_device)."""
+        import torch
+        h = self._require()
+        t = torch.empty(self._nnz(), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        check(self._L.sm_copy_term_ids_device(h, _ptr(t) if t.numel() else 0, _stream_of(t, stream)),
+              "sm_copy_term_ids_device")
+        return t
+
+    def sddmm_table(self, G, X, out=None, alpha: float = 1.0, beta: float = 0.0, algo="auto",
+                    stream=None):
+        """out[t] = alpha * sum over the terms e with id t of <G[r_e, :], X[c_e, :]> + beta * out[t]
+        (sm_sddmm_table): with G = dL/dY, the gradient of the table of Y = alpha * B * X, in one
+        deterministic fused pass (no nnz-sized array).  G and X as for sddmm; alpha == 0 takes
+        G = X = None.  `out`: T float32 elements on the matrix's device (any 4-byte alignment);
+        None allocates zeros.  Returns `out`."""
+        import torch
+        n_rows, n_cols = self._dims()
+        h = self._require()
+        T = self._table_size()
+        if alpha == 0.0 and G is None and X is None:
+            n_rhs, ldg, ldx = 1, 1, 1
+        else:
+            n_rhs, ldg = _sddmm_operand(G, n_rows, "G")
+            n_x, ldx = _sddmm_operand(X, n_cols, "X")
+            if n_x != n_rhs:
+                raise ValueError(f"G has {n_rhs} columns, X has {n_x}")
+            if n_rhs < 1:
+                raise ValueError("G and X need at least one column")
+            if G.device != X.device:
+                raise ValueError("G and X must be on the same device")
+        if out is None:
+            out = torch.zeros(T, dtype=torch.float32, device=torch.device("cuda", self.device))
+        else:
+            self._table_operand(out, "out")
+        st = self._L.sm_sddmm_table(h, n_rhs, alpha, _ptr(G), ldg, _ptr(X), ldx, beta, _ptr(out),
+                                    _algo(algo), _stream_of(out, stream))
+        check(st, "sm_sddmm_table")
+        return out
+
+    def _table_operand(self, t, name: str) -> None:
+        T = self._table_size()
+        _check_dev(t, T, name)
+        if T == 0:   # not a table matrix (or an empty one): the library answers
+            return
+        if t.dim() != 1 or t.numel() != T or (T > 1 and t.stride(0) != 1):
+            raise ValueError(f"{name} must be a unit-stride 1-D tensor of T = {T} elements")
+        if t.device.index != self.device:
+            raise ValueError(f"{name} must be on the matrix's device")
+
+    def set_table(self, t, stream=None) -> None:
+        """table[i] = t[i], bit for bit (sm_set_table), on a matrix built by from_csr_ids with
+        ``opts={"table_updatable": 1}``: afterwards the matrix is what from_csr_ids builds from the
+        same pattern and ids with the new table, every layout and product bit for bit.  `t`: T
+        float32 elements on the matrix's device.  Asynchronous on `stream`, capturable; a cached
+        transposed companion (T) takes the same call on the same stream.  The call writes the
+        matrix: order it against products of this matrix on other streams."""
+        h = self._require()
+        self._table_operand(t, "t")
+        s = _stream_of(self, stream)
+        check(self._L.sm_set_table(h, _ptr(t), s), "sm_set_table")
+        if self._t is not None:
+            check(self._L.sm_set_table(self._t._require(), _ptr(t), s), "sm_set_table (T)")
+
+    def axpy_table(self, a: float, delta, stream=None) -> None:
+        """table[i] = fl(table[i] + fl(a * delta[i])) (sm_axpy_table; two roundings, no fused
+        multiply-add) -- an optimiser step on the table, e.g. ``m.axpy_table(-lr, grad)`` with the
+        gradient sddmm_table gives.  a == 0 does nothing and `delta` may then be None.  Stream
+        behaviour and the companion T as for set_table."""
+        h = self._require()
+        a = float(a)
+        if a != 0.0 or delta is not None:
+            self._table_operand(delta, "delta")
+        s = _stream_of(self, stream)
+        check(self._L.sm_axpy_table(h, a, _ptr(delta), s), "sm_axpy_table")
+        if self._t is not None:
+            check(self._L.sm_axpy_table(self._t._require(), a, _ptr(delta), s), "sm_axpy_table (T)")
 
     def csr_device(self, stream=None):
         """(row_ptr, col_idx, val): new torch tensors on the matrix's device holding its CSR
