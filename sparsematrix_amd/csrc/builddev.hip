@@ -1,5 +1,5 @@
 // builddev.hip -- the column relabeling and the sorted sliced ELL built on the device from a
-// device CSR: the same bytes the host builders produce (capi.cpp
+// device CSR: the same bytes the host builders produce (layouts.cpp
 // upload_relabel, sell.cpp sell_build, xband.h codebook_ids), without copying the terms to the
 // host and back.  R-MAT scale 24 (config 4, 263 M terms) took 5.4 s on the host path.
 //
@@ -239,28 +239,6 @@ __global__ __launch_bounds__(256) void bd_mstage_kernel(int64_t n, const unsigne
     }
 }
 
-struct Tmp {
-    std::vector<void *> p;
-    template <class T>
-    hipError_t alloc(T **out, int64_t n) {
-        *out = nullptr;
-        const hipError_t e = hipMalloc((void **)out, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-    ~Tmp() {
-        for (void *q : p) (void)hipFree(q);
-    }
-};
-
-template <class T>
-hipError_t keep_alloc(T **out, int64_t n, int64_t &acct) {
-    const size_t bytes = (size_t)std::max<int64_t>(n, 1) * sizeof(T);
-    const hipError_t e = hipMalloc((void **)out, bytes);
-    if (e == hipSuccess) acct += (int64_t)bytes;
-    return e;
-}
-
 #define BD_TRY(x)                  \
     do {                           \
         const hipError_t e_ = (x); \
@@ -271,7 +249,7 @@ hipError_t keep_alloc(T **out, int64_t n, int64_t &acct) {
     } while (0)
 
 template <class K, class V>
-hipError_t sort_pairs(Tmp &t, const K *k, K *ks, const V *v, V *vs, int64_t n, int end_bit, hipStream_t s) {
+hipError_t sort_pairs(DevScratch &t, const K *k, K *ks, const V *v, V *vs, int64_t n, int end_bit, hipStream_t s) {
     size_t bytes = 0;
     hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k, ks, v, vs, (int)n, 0, end_bit, s);
     if (e != hipSuccess) return e;
@@ -281,7 +259,7 @@ hipError_t sort_pairs(Tmp &t, const K *k, K *ks, const V *v, V *vs, int64_t n, i
 }
 
 template <class T, class O>
-hipError_t excl_sum(Tmp &t, const T *in, O *out, int64_t n, hipStream_t s) {
+hipError_t excl_sum(DevScratch &t, const T *in, O *out, int64_t n, hipStream_t s) {
     size_t bytes = 0;
     hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, s);
     if (e != hipSuccess) return e;
@@ -302,7 +280,7 @@ int devbuild_relabel(sm_matrix *m, bool check_skew, hipStream_t s, hipError_t &e
     err = hipSuccess;
     Plan &p = m->plan;
     const int64_t nc = m->n_cols, nnz = m->nnz;
-    Tmp t;
+    DevScratch t;
     int32_t *deg = nullptr, *dmx = nullptr, *idx = nullptr, *perm = nullptr;
     uint32_t *key = nullptr, *skey = nullptr;
     unsigned long long *hot = nullptr;
@@ -326,7 +304,7 @@ int devbuild_relabel(sm_matrix *m, bool check_skew, hipStream_t s, hipError_t &e
     BD_TRY(hipGetLastError());
     BD_TRY(sort_pairs(t, key, skey, idx, perm, nc, bits_for((uint32_t)dmax), s));
     int32_t *rank = nullptr;
-    BD_TRY(keep_alloc(&p.d_perm, nc + 4, m->device_bytes));
+    BD_TRY(m->mem.alloc(&p.d_perm, nc + 4));
     rank = p.d_perm;
     hipLaunchKernelGGL(bd_rank_kernel, dim3(grid_of(nc)), dim3(256), 0, s, nc, perm, skey, dmax, nc / 16, rank, hot);
     BD_TRY(hipGetLastError());
@@ -334,13 +312,11 @@ int devbuild_relabel(sm_matrix *m, bool check_skew, hipStream_t s, hipError_t &e
     BD_TRY(hipMemcpyAsync(&hot_h, hot, 8, hipMemcpyDeviceToHost, s));
     BD_TRY(hipStreamSynchronize(s));
     if (check_skew && (double)hot_h < 0.4 * (double)nnz) {   // not skewed: no gain (upload_relabel)
-        (void)hipFree(p.d_perm);
-        m->device_bytes -= (int64_t)(nc + 4) * 4;
-        p.d_perm = nullptr;
+        m->mem.release(p.d_perm);
         return 0;
     }
-    BD_TRY(keep_alloc(&p.d_rcol, nnz + kPadElems, m->device_bytes));
-    BD_TRY(keep_alloc(&p.d_xperm, nc + 4, m->device_bytes));
+    BD_TRY(m->mem.alloc(&p.d_rcol, nnz + kPadElems));
+    BD_TRY(m->mem.alloc(&p.d_xperm, nc + 4));
     hipLaunchKernelGGL(bd_remap_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, m->d_col, rank, p.d_rcol);
     BD_TRY(hipGetLastError());
     BD_TRY(hipMemsetAsync(p.d_rcol + nnz, 0, kPadElems * sizeof(int32_t), s));
@@ -354,7 +330,7 @@ int devbuild_codebook(const float *d_val, int64_t n, std::vector<float> &table, 
     err = hipSuccess;
     table.clear();
     if (n <= 0) return 0;
-    Tmp t;
+    DevScratch t;
     uint32_t *bits = nullptr, *bits_s = nullptr, *hb = nullptr;
     int32_t *idx = nullptr, *idx_s = nullptr, *nh = nullptr, *hi = nullptr;
     BD_TRY(t.alloc(&bits, n));
@@ -412,7 +388,7 @@ int devbuild_merge_stage(sm_matrix *m, hipStream_t s, hipError_t &err) {
     if (nnz <= 0 || m->n_cols > (1 << 24) || !p.d_merge_corner) return 1;   // merge_stage_build declines
     const int32_t *col = p.n_relabel > 0 ? p.d_rcol : m->d_col;
     const int32_t *corner = reinterpret_cast<const int32_t *>(p.d_merge_corner);
-    Tmp t;
+    DevScratch t;
     uint8_t *ids = nullptr;
     BD_TRY(t.alloc(&ids, nnz));
     std::vector<float> table;
@@ -429,9 +405,9 @@ int devbuild_merge_stage(sm_matrix *m, hipStream_t s, hipError_t &err) {
                        key, idx);
     BD_TRY(hipGetLastError());
     BD_TRY(sort_pairs(t, key, skey, idx, sidx, nnz, 24 + bits_for((uint32_t)std::max<int64_t>(nb - 1, 1)), s));
-    BD_TRY(keep_alloc(&p.d_mstage_w, nnz, m->device_bytes));
-    BD_TRY(keep_alloc(&p.d_mstage_z, nnz, m->device_bytes));
-    BD_TRY(keep_alloc(&p.d_mstage_tab, 256, m->device_bytes));
+    BD_TRY(m->mem.alloc(&p.d_mstage_w, nnz));
+    BD_TRY(m->mem.alloc(&p.d_mstage_z, nnz));
+    BD_TRY(m->mem.alloc(&p.d_mstage_tab, 256));
     table.resize(256, 0.0f);
     BD_TRY(hipMemcpy(p.d_mstage_tab, table.data(), 256 * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(bd_mstage_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, skey, sidx, corner, col, ids,
@@ -446,7 +422,7 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
     Plan &p = m->plan;
     const int64_t nr = m->n_rows, nnz = m->nnz;
     const int32_t *col = p.n_relabel > 0 ? p.d_rcol : m->d_col;
-    Tmp t;
+    DevScratch t;
     // codebook ids (sell_upload: columns < 2^24 and <= 255 distinct patterns)
     std::vector<float> table;
     uint8_t *ids = nullptr;
@@ -483,9 +459,9 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
     SellDev &d = p.sell;
     d.max_len = max_len;
     d.n_long = n_long;
-    BD_TRY(keep_alloc(&d.d_long_rows, n_long, m->device_bytes));
-    BD_TRY(keep_alloc(&d.d_long_ptr, n_long + 1, m->device_bytes));
-    BD_TRY(keep_alloc(&d.d_partials, n_parts, m->device_bytes));
+    BD_TRY(m->mem.alloc(&d.d_long_rows, n_long));
+    BD_TRY(m->mem.alloc(&d.d_long_ptr, n_long + 1));
+    BD_TRY(m->mem.alloc(&d.d_partials, n_parts));
     BD_TRY(hipMemsetAsync(d.d_long_ptr, 0, 4, s));
     int32_t *urow = nullptr, *ustart = nullptr, *un = nullptr, *upart = nullptr, *uidx = nullptr, *order = nullptr;
     uint32_t *ukey = nullptr, *ukey_s = nullptr;
@@ -505,8 +481,8 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
     const int64_t ns = (U + kSellLanes - 1) / kSellLanes;
     int64_t *slots = nullptr;
     BD_TRY(t.alloc(&slots, ns + 1));
-    BD_TRY(keep_alloc(&d.d_off, ns, m->device_bytes));
-    BD_TRY(keep_alloc(&d.d_len, ns, m->device_bytes));
+    BD_TRY(m->mem.alloc(&d.d_off, ns));
+    BD_TRY(m->mem.alloc(&d.d_len, ns));
     BD_TRY(hipMemsetAsync(slots + ns, 0, 8, s));
     hipLaunchKernelGGL(bd_slice_len_kernel, dim3(grid_of(ns)), dim3(256), 0, s, ns, U, order, un, d.d_len, slots);
     BD_TRY(hipGetLastError());
@@ -518,24 +494,23 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
     BD_TRY(hipMemcpyAsync(d.d_off, offs, (size_t)ns * 8, hipMemcpyDeviceToDevice, s));
     BD_TRY(hipStreamSynchronize(s));
     if (ns == 0 || padded >= ((int64_t)1 << 31) - kSellLanes * kSellUnroll) {   // upload_sell declines
-        (void)hipFree(d.d_long_rows), (void)hipFree(d.d_long_ptr), (void)hipFree(d.d_partials);
-        (void)hipFree(d.d_off), (void)hipFree(d.d_len);
+        m->mem.release(d.d_long_rows, d.d_long_ptr, d.d_partials, d.d_off, d.d_len);
         d = SellDev();
         return 0;
     }
-    BD_TRY(keep_alloc(&d.d_row, ns * kSellLanes, m->device_bytes));
-    BD_TRY(keep_alloc(&d.d_row_len, ns * kSellLanes, m->device_bytes));
+    BD_TRY(m->mem.alloc(&d.d_row, ns * kSellLanes));
+    BD_TRY(m->mem.alloc(&d.d_row_len, ns * kSellLanes));
     BD_TRY(hipMemsetAsync(d.d_row, 0xFF, (size_t)ns * kSellLanes * 4, s));   // -1: no row
     BD_TRY(hipMemsetAsync(d.d_row_len, 0, (size_t)ns * kSellLanes * 4, s));
     const int64_t tail = 32 * kSellLanes;
-    BD_TRY(keep_alloc(&d.d_col, padded + tail, m->device_bytes));
+    BD_TRY(m->mem.alloc(&d.d_col, padded + tail));
     BD_TRY(hipMemsetAsync(d.d_col, 0, (size_t)(padded + tail) * 4, s));
     if (cb) {
-        BD_TRY(keep_alloc(&d.d_table, std::max<int64_t>((int64_t)table.size(), 1), m->device_bytes));
+        BD_TRY(m->mem.alloc(&d.d_table, std::max<int64_t>((int64_t)table.size(), 1)));
         if (!table.empty()) BD_TRY(hipMemcpy(d.d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice));
         d.table_size = (int32_t)table.size();
     } else {
-        BD_TRY(keep_alloc(&d.d_val, padded + tail, m->device_bytes));
+        BD_TRY(m->mem.alloc(&d.d_val, padded + tail));
         BD_TRY(hipMemsetAsync(d.d_val, 0, (size_t)(padded + tail) * 4, s));
     }
     const unsigned gf = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ns + 3) / 4, 1 << 16));

@@ -352,36 +352,6 @@ __global__ __launch_bounds__(256) void gk_max_kernel(int64_t n, const int32_t *_
     if ((threadIdx.x & 63) == 0) atomicMax(out, mx);
 }
 
-struct Tmp {
-    std::vector<void *> p;
-    template <class T>
-    hipError_t alloc(T **out, int64_t n) {
-        *out = nullptr;
-        const hipError_t e = hipMalloc((void **)out, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-    void release(void *q) {
-        for (auto &x : p)
-            if (x == q) {
-                (void)hipFree(x);
-                x = nullptr;
-            }
-    }
-    ~Tmp() {
-        for (void *q : p)
-            if (q) (void)hipFree(q);
-    }
-};
-
-template <class T>
-hipError_t keep_alloc_dev(T **out, int64_t n, int64_t &acct) {
-    const size_t bytes = (size_t)std::max<int64_t>(n, 1) * sizeof(T);
-    const hipError_t e = hipMalloc((void **)out, bytes);
-    if (e == hipSuccess) acct += (int64_t)bytes;
-    return e;
-}
-
 #define GK_TRY(x)                  \
     do {                           \
         const hipError_t e_ = (x); \
@@ -415,7 +385,7 @@ int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, G
     if (ntile >= ((int64_t)1 << 30)) return 1;
     const int cbits = bits_for((uint64_t)(n_cols - 1));
     const int end_bit = cbits + bits_for((uint64_t)std::max<int64_t>(nblk - 1, 1));
-    Tmp tp;
+    DevScratch tp;
     unsigned long long *key = nullptr, *skey = nullptr;
     int32_t *idx = nullptr, *sidx = nullptr, *rowl = nullptr, *flag = nullptr;
     GK_TRY(tp.alloc(&key, nnz));
@@ -468,7 +438,7 @@ int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, G
     GK_TRY(hipMemsetAsync(mx, 0, 4, s));
     hipLaunchKernelGGL(gk_cut_kernel, dim3((unsigned)ntile), dim3(kCutThreads), 0, s, tts, scol, srl, window, bstart, nb);
     GK_TRY(hipGetLastError());
-    GK_TRY(keep_alloc_dev(&m->plan.xb.d_chunk_start, ntile + 1, m->device_bytes));
+    GK_TRY(m->mem.alloc(&m->plan.xb.d_chunk_start, ntile + 1));
     tbs = m->plan.xb.d_chunk_start;
     {
         size_t bytes = 0;
@@ -485,9 +455,7 @@ int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, G
     GK_TRY(hipStreamSynchronize(s));
     // gcb_build's output limits: a tile's bands under 4 GiB of 32-bit byte offsets.
     if ((int64_t)max_bands * kGcbBandWords * 4 >= ((int64_t)1 << 32) || n_bands <= 0 || n_bands >= INT32_MAX) {
-        (void)hipFree(m->plan.xb.d_chunk_start);
-        m->device_bytes -= (ntile + 1) * 4;
-        m->plan.xb.d_chunk_start = nullptr;
+        m->mem.release(m->plan.xb.d_chunk_start);
         return 1;
     }
     int32_t *gstart = nullptr, *gtile = nullptr;
@@ -497,8 +465,8 @@ int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, G
                        tts, tbs, bstart, gstart, gtile);
     GK_TRY(hipGetLastError());
     XbandDev &d = m->plan.xb;
-    GK_TRY(keep_alloc_dev(&d.d_band_clo, n_bands, m->device_bytes));
-    GK_TRY(keep_alloc_dev(&d.d_word, (int64_t)n_bands * kGcbBandWords, m->device_bytes));
+    GK_TRY(m->mem.alloc(&d.d_band_clo, n_bands));
+    GK_TRY(m->mem.alloc(&d.d_word, (int64_t)n_bands * kGcbBandWords));
     hipLaunchKernelGGL(gk_emit_kernel, dim3((unsigned)n_bands), dim3(kCutThreads), 0, s, (int64_t)n_bands, tts, gstart,
                        gtile, scol, srl, sval, d.d_band_clo, d.d_word, flag);
     GK_TRY(hipGetLastError());

@@ -20,7 +20,7 @@
 //
 // Stream ordering of the gather buffers: every product records `consumed[b]` on the
 // stream that read xbuf[b]; every all-gather into xbuf[b] first waits for it, whatever
-// stream either runs on (the same contract as the matrix's scratch, capi.cpp).
+// stream either runs on (the same contract as the matrix's scratch, sm_internal.h with_turn).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -33,6 +33,7 @@
 #include <mutex>
 #include <string>
 
+#include "capi_util.h"
 #include "sm_internal.h"
 
 namespace {
@@ -129,21 +130,8 @@ sm_status nccl_fail(ncclResult_t r, const char *what) {
                  (int)r);
 }
 
-struct DevScope {
-    int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit DevScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevScope() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 void release(sm_multi *mc) {
-    DevScope g(mc->device);
+    smamd::DeviceGuard g(mc->device);
     (void)hipDeviceSynchronize();   // no product may still use the buffers or events
     if (mc->comm && rccl_ok()) (void)rccl().comm_destroy(mc->comm);
     for (int i = 0; i < 2; ++i) {
@@ -274,7 +262,7 @@ sm_status create_common(int32_t nranks, int32_t rank, const sm_matrix *local, sm
     mc->local = local;
     mc->n_cols = info.n_cols;
     mc->x_local_len = info.n_cols / nranks;
-    DevScope g(mc->device);
+    smamd::DeviceGuard g(mc->device);
     hipError_t e = g.err;
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&mc->comm_stream, hipStreamNonBlocking);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
@@ -312,7 +300,7 @@ sm_status sm_multi_create(const sm_unique_id *id, int32_t nranks, int32_t rank,
         delete mc;
         return mfail(SM_ERR_NOT_SUPPORTED, "%s", rccl().why.c_str());
     }
-    DevScope g(mc->device);
+    smamd::DeviceGuard g(mc->device);
     ncclUniqueId u;
     memcpy(&u, id, sizeof(u));
     const ncclResult_t r = rccl().comm_init_rank(&mc->comm, nranks, u, rank);   // collective
@@ -353,7 +341,7 @@ sm_status sm_multi_set_timing(sm_multi *mc, int32_t on) {
 sm_status sm_multi_last_times(sm_multi *mc, float *allgather_ms, float *compute_ms) {
     if (!mc) return mfail(SM_ERR_INVALID_ARG, "null context");
     if (!mc->timing) return mfail(SM_ERR_NOT_SUPPORTED, "timing is off (sm_multi_set_timing)");
-    DevScope g(mc->device);
+    smamd::DeviceGuard g(mc->device);
     hipError_t e = hipEventSynchronize(mc->t2);
     float a = 0.f, b = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&a, mc->t0, mc->t1);
@@ -370,7 +358,7 @@ sm_status sm_multi_allgather(sm_multi *mc, const float *x_local, int32_t n_rhs, 
     if (n_rhs < 1 || (!x_local && mc->x_local_len > 0))
         return mfail(SM_ERR_INVALID_ARG, "bad x_local / n_rhs");
     std::lock_guard<std::mutex> lk(mc->mu);
-    DevScope g(mc->device);
+    smamd::DeviceGuard g(mc->device);
     hipStream_t s = (hipStream_t)stream;
     sm_status st = ensure_buffers(mc, (size_t)mc->n_cols * n_rhs, s);
     if (st == SM_OK) st = order_write(mc, 0, s);
@@ -417,7 +405,7 @@ sm_status sm_multi_spmv(sm_multi *mc, float alpha, const float *x_local, float b
     if (!mc) return mfail(SM_ERR_INVALID_ARG, "null context");
     if (!y_local || (!x_local && mc->x_local_len > 0)) return mfail(SM_ERR_INVALID_ARG, "null x/y");
     std::lock_guard<std::mutex> lk(mc->mu);
-    DevScope g(mc->device);
+    smamd::DeviceGuard g(mc->device);
     return one_product(mc, 0, alpha, x_local, beta, y_local, 1, algo, (hipStream_t)stream);
 }
 
@@ -427,7 +415,7 @@ sm_status sm_multi_spmm(sm_multi *mc, int32_t n_rhs, float alpha, const float *X
     if (n_rhs < 1 || ldy < n_rhs || !Y_local || (!X_local && mc->x_local_len > 0))
         return mfail(SM_ERR_INVALID_ARG, "bad SpMM arguments");
     std::lock_guard<std::mutex> lk(mc->mu);
-    DevScope g(mc->device);
+    smamd::DeviceGuard g(mc->device);
     return one_product(mc, n_rhs, alpha, X_local, beta, Y_local, ldy, algo, (hipStream_t)stream);
 }
 
@@ -449,7 +437,7 @@ sm_status sm_multi_spmv_batch(sm_multi *mc, int32_t count, const sm_matrix *cons
             return mfail(SM_ERR_INVALID_ARG, "batch product %d: null x/y", i);
     if (count == 0) return SM_OK;
     std::lock_guard<std::mutex> lk(mc->mu);
-    DevScope g(mc->device);
+    smamd::DeviceGuard g(mc->device);
     hipStream_t s = (hipStream_t)stream, c = mc->comm_stream;
     sm_status st = ensure_buffers(mc, (size_t)mc->n_cols, s);
     if (st != SM_OK) return st;

@@ -915,15 +915,15 @@ hipError_t launch_native_addmatmat(const NativeDev &nd, int32_t m, const float *
 #ifdef SM_DEV
             if (m == 1 && !bitmap && dev_env("SM_NAT_TS")) {   // the decode again, stamped (same outputs)
                 const int64_t nw = (int64_t)nd.n_batches;
+                DevScratch tmp;
                 unsigned long long *d = nullptr;
                 std::vector<unsigned long long> h((size_t)nw * 4);
-                if (hipMalloc(&d, h.size() * 8) != hipSuccess) return hipErrorOutOfMemory;
+                if (tmp.alloc(&d, (int64_t)h.size()) != hipSuccess) return hipErrorOutOfMemory;
                 hipLaunchKernelGGL((native_decode_batch_kernel<true, true>), dim3((unsigned)nd.n_batches), dim3(1024), 0,
                                    s, nd.d_pos, nd.d_val, nd.d_bmeta, nd.d_boff, nd.d_table, nd.table_size, a,
                                    alpha, nd.d_lists, nd.d_hdr, d);
                 (void)hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, s);
                 (void)hipStreamSynchronize(s);
-                (void)hipFree(d);
                 unsigned long long t0 = ~0ull, t1 = 0;
                 for (int64_t i = 0; i < nw; i++) t0 = std::min(t0, h[(size_t)(4 * i)]), t1 = std::max(t1, h[(size_t)(4 * i + 3)]);
                 std::vector<double> st, life, load, rank, tail;
@@ -945,8 +945,9 @@ hipError_t launch_native_addmatmat(const NativeDev &nd, int32_t m, const float *
                         pct(load, .5), pct(load, .9), pct(rank, .5), pct(rank, .9), pct(tail, .5), pct(tail, .9));
             }
             if (dev_env("SM_NAT_PROF")) {   // the decode again, profiled (same outputs)
+                DevScratch tmp;
                 unsigned long long *d = nullptr, h[8] = {};
-                if (hipMalloc(&d, sizeof(h)) != hipSuccess) return hipErrorOutOfMemory;
+                if (tmp.alloc(&d, 8) != hipSuccess) return hipErrorOutOfMemory;
                 (void)hipMemsetAsync(d, 0, sizeof(h), s);
                 if (m == 1)
                     hipLaunchKernelGGL((native_decode_kernel<true, true>), dgrid, dim3(kNatThreads), 0, s,
@@ -958,7 +959,6 @@ hipError_t launch_native_addmatmat(const NativeDev &nd, int32_t m, const float *
                                        nd.table_size, a, alpha, nd.d_lists, nd.d_hdr, d);
                 (void)hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s);
                 (void)hipStreamSynchronize(s);
-                (void)hipFree(d);
                 const double w = (double)h[7];
                 fprintf(stderr, "native decode prof (kcycles per workgroup, %.0f wgs): meta+load %.2f scan %.2f "
                         "mark %.2f rank1 %.2f rank2 %.2f place+drain %.2f\n", w, h[0] / w / 1e3, h[1] / w / 1e3,
@@ -997,13 +997,13 @@ hipError_t launch_native_addmatmat(const NativeDev &nd, int32_t m, const float *
     } while (0)
 #ifdef SM_DEV
     if (dev_env("SM_NAT_PROF")) {   // per-phase cycles, summed over workgroups, to stderr
+        DevScratch tmp;
         unsigned long long *d = nullptr, h[8] = {};
-        if (hipMalloc(&d, sizeof(h)) != hipSuccess) return hipErrorOutOfMemory;
+        if (tmp.alloc(&d, 8) != hipSuccess) return hipErrorOutOfMemory;
         (void)hipMemsetAsync(d, 0, sizeof(h), s);
         SM_NAT_ALL(true, d);
         (void)hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s);
         (void)hipStreamSynchronize(s);
-        (void)hipFree(d);
         const double wgs = (double)h[7];
         fprintf(stderr, "native prof (kcycles per workgroup, %.0f wgs): init %.2f scan %.2f mark %.2f "
                 "rank1 %.2f rank2 %.2f place %.2f apply %.2f\n", wgs, h[0] / wgs / 1e3, h[1] / wgs / 1e3,

@@ -143,20 +143,6 @@ unsigned grid_for(int64_t n) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16));
 }
 
-struct DevBufs {
-    std::vector<void *> p;
-    template <class T>
-    hipError_t alloc(T **out, int64_t n) {
-        *out = nullptr;
-        const hipError_t e = hipMalloc((void **)out, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-    ~DevBufs() {
-        for (void *q : p) (void)hipFree(q);
-    }
-};
-
 #define RE_TRY(x)                   \
     do {                            \
         const hipError_t e_ = (x);  \
@@ -176,7 +162,7 @@ int encode_csr_ref_device(const int32_t *d_rp, const int32_t *d_col, const float
     if (n_cols >= ((int64_t)1 << (31 - kPanelShift))) return -4;
     if (table && (table_size < 0 || table_size > (int32_t)kMaxStep)) return -1;
     if (d_ids && !table) return -1;
-    DevBufs b;
+    DevScratch b;
     const unsigned g_rows = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_rows + 3) / 4, 1 << 16));
     // ---- the codebook: value bits -> id (the first entry with those bits) ----------------
     std::vector<std::pair<uint32_t, uint8_t>> book;   // sorted by bits

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "sparsematrix.h"
+#include "devmem.h"
 #include "merge.h"
 
 namespace smamd {
@@ -37,29 +38,44 @@ inline const char *dev_env(const char *name) {
 #endif
 }
 
-// Resolved layout options (sm_build_opts with defaults filled in).
-struct BuildOpts {
-    int32_t layout = SM_LAYOUT_AUTO;
-    int32_t band_slabs = 0;
-    int32_t band_tall = 0;
-    int32_t gather_band_log2 = 0;
-    int32_t sell = -1;
-    int32_t sell_codebook = -1;
-    int32_t sell_max_len = 0;
-    int32_t sell_streams = 0;
-    int64_t sell_sigma = 0;
-    int32_t relabel = -1;
-    int32_t tile_nnz = 0;
-    int32_t ccsell = -1;
-    int32_t ccsell_chunk_log2 = 0;
-    int32_t hot_cols = 0;
-    int32_t exact_sell = 0;   // 0 auto, 1 always, -1 never (sm_build_opts.exact_sell)
-    int32_t band_slab0_permille = 0;   // 0 auto (sm_build_opts.band_slab0_permille)
-    int32_t merge_stage = 0;           // sm_build_opts.merge_stage
-    int32_t host_build = 0;            // sm_build_opts.host_build
-    int32_t updatable = 0;             // sm_build_opts.updatable
-    int32_t table_updatable = 0;       // sm_build_opts.table_updatable
+// Resolved layout options: sm_build_opts with the defaults of sm_build_opts_init filled in for
+// what the caller's struct_size leaves out (resolve_opts, layouts.cpp).
+using BuildOpts = sm_build_opts;
+
+// Taking turns on scratch that belongs to a matrix (slab partials and hand-off words, long-row
+// partials, the relabeled x; the table gradient's partials): work that uses it runs one after
+// the other on the device, whatever stream or thread issues it -- correct, the way the
+// reference's read-only AddMatMat allows concurrent callers (sparse-matrix.cc:139-194).
+struct Turn {
+    std::mutex mu;
+    hipEvent_t ready = nullptr;   // recorded after the previous user's last launch
+    bool recorded = false;
 };
+
+// Runs `launch` (which queues on `s` and returns its hipError_t) as the next user of the
+// turn's scratch: the stream waits for the previous user's event and records it after its own
+// launches, also when one failed (whatever was queued uses the scratch).  A stream being
+// captured into a graph is ordered by that stream alone: no event is waited on or recorded.
+// `needed` false: the launch uses no scratch and takes no turn.
+template <class F>
+hipError_t with_turn(Turn &t, hipStream_t s, bool needed, F &&launch) {
+    if (!needed) return launch();
+    std::lock_guard<std::mutex> lk(t.mu);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
+    const bool ordered = cs == hipStreamCaptureStatusNone;
+    hipError_t e = hipSuccess;
+    if (ordered && !t.ready) e = hipEventCreateWithFlags(&t.ready, hipEventDisableTiming);
+    if (ordered && e == hipSuccess && t.recorded) e = hipStreamWaitEvent(s, t.ready, 0);
+    if (e != hipSuccess) return e;
+    e = launch();
+    if (ordered) {
+        const hipError_t er = hipEventRecord(t.ready, s);
+        if (er == hipSuccess) t.recorded = true;
+        if (e == hipSuccess) e = er;
+    }
+    return e;
+}
 
 // Row tile: rows [r0, r1) whose terms fit one LDS tile.  flags bit0: the tile
 // holds a row longer than kSerialRowMax (wave-parallel reduction pass needed).
@@ -349,6 +365,28 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
 // The merge path's staging stream (merge_stage_build's bytes) from the device CSR and the
 // plan's slice corners: 0 built, 1 declined as the host would, < 0 on a HIP error (err).
 int devbuild_merge_stage(sm_matrix *m, hipStream_t s, hipError_t &err);
+// Layout decisions and host builders (layouts.cpp), which the constructors of capi.cpp end in.
+// resolve_opts: the caller's sm_build_opts with defaults for what its struct_size leaves out
+// and, in -DSM_DEV builds only, the SM_* development variables on top.  check_opts: the
+// options' ranges and exclusions (`table_ok`: the constructor builds a table matrix, the only
+// ones that honour table_updatable).
+BuildOpts resolve_opts(const sm_build_opts *o);
+sm_status check_opts(const sm_build_opts *o, bool table_ok = false);
+// The CSR arrays of `m` (its sizes set): col / val carry a zeroed tail of kPadElems.
+sm_status alloc_csr(sm_matrix *m);
+// Common tails of the constructors.  Host CSR: uploads it, plans and builds the layouts.
+// Device CSR: `m` holds its sizes, options and the CSR arrays (alloc_csr) filled on `s`;
+// validates them by a kernel, plans, and builds the layouts on the device or the host as the
+// options ask; synchronises `s`.  `exact_sell`: also the unsegmented sliced ELL where
+// want_exact_sell asks for it (the host constructors' last step).
+sm_status finish_from_host_csr(sm_matrix *m, const int32_t *rp, const int32_t *col, const float *val);
+sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell);
+// The reference's stream the matrix holds on the host, on the device (native.hip).
+sm_status upload_native(sm_matrix *m);
+// SM_ALGO_EXACT's choice for `m` (x 16-byte aligned: `x16`): an sm_algo, or kAlgoExactSell
+// for the unsegmented sliced ELL built for it.
+constexpr int kAlgoExactSell = 100;
+int exact_algo(const sm_matrix *m, bool x16);
 // The gathered chunk bands (builddev_gcb.hip): gcb_build's bytes into m->plan.xb's d_chunk_start,
 // d_band_clo and d_word, the geometry in `meta` (its vectors stay empty).  0 built, 1 declined as
 // gcb_build would, < 0 on a HIP error (err) or a builder inconsistency.
@@ -416,7 +454,10 @@ struct sm_matrix {
     float *d_val = nullptr;
     smamd::Plan plan;
     smamd::BuildOpts opts;                     // layout options the matrix was built with
-    int64_t device_bytes = 0;
+    // Every device buffer the matrix keeps (the raw d_* pointers here and in `plan` point into
+    // it); mem.bytes is sm_info.device_bytes.  ~sm_matrix frees them all.
+    smamd::DevMem mem;
+    ~sm_matrix();
     // Reference encoding (only for matrices built by sm_create_from_dense_index).
     bool has_ref = false;
     bool from_index = false;   // built by the CopyForm constructors (the reference's path)
@@ -434,18 +475,16 @@ struct sm_matrix {
     bool has_src_term = false;   // (also true with nnz == 0, where there is nothing to allocate)
     // Table matrix (sm_create_from_csr_ids and its transposes): the terms' ids (nnz bytes, CSR
     // order) and the authoritative table (256 floats, zero past tab_size) on the device, and the
-    // per-chunk partials of sm_sddmm_table (tab_chunks * kTablePartialStride floats) with the
-    // event that makes its calls take turns (as scratch_ready does for the SpMVs).  These fields
-    // are apart from table / d_term_ids above, whose invariants belong to the dense-index path.
+    // per-chunk partials of sm_sddmm_table (tab_chunks * kTablePartialStride floats), used in
+    // turn (table_turn).  These fields are apart from table / d_term_ids above, whose invariants
+    // belong to the dense-index path.
     bool is_table = false;
     int32_t tab_size = 0;
     uint8_t *d_tab_ids = nullptr;
     float *d_tab = nullptr;
     float *d_tab_partials = nullptr;
     int64_t tab_chunks = 0;
-    mutable std::mutex tab_mu;
-    mutable hipEvent_t tab_ready = nullptr;
-    mutable bool tab_recorded = false;
+    mutable smamd::Turn table_turn;
     // While a table_updatable matrix is being built: the host copies the layout builders take
     // their ids and table from (owned by the constructor; null afterwards).
     const uint8_t *build_ids = nullptr;
@@ -461,14 +500,7 @@ struct sm_matrix {
     mutable float *d_ws = nullptr;
     mutable size_t ws_bytes = 0;
     mutable hipEvent_t ws_ready = nullptr;
-    // SpMV scratch (slab partials and hand-off words, long-row partials, the relabeled
-    // x) belongs to the matrix: every SpMV that uses it makes its stream wait on
-    // scratch_ready (recorded after the previous such SpMV's kernels), so SpMVs on one
-    // matrix from several streams or threads run one after the other on the device,
-    // correct, the way the reference's read-only AddMatMat allows concurrent callers
-    // (sparse-matrix.cc:139-194).  Calls into a stream being captured are ordered by
-    // that stream alone.
-    mutable std::mutex scratch_mu;
-    mutable hipEvent_t scratch_ready = nullptr;
-    mutable bool scratch_recorded = false;
+    // SpMV scratch (slab partials and hand-off words, long-row partials, the relabeled x, the
+    // native form's column lists) belongs to the matrix: SpMVs that use it take turns.
+    mutable smamd::Turn scratch_turn;
 };

@@ -88,20 +88,6 @@ __global__ __launch_bounds__(256) void tr_narrow_kernel(int64_t nnz, const uint3
     GS_LOOP(j, nnz) ids[j] = (uint8_t)wide[j];
 }
 
-struct Tmp {
-    std::vector<void *> p;
-    template <class T>
-    hipError_t alloc(T **out, int64_t n) {
-        *out = nullptr;
-        const hipError_t e = hipMalloc((void **)out, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-    ~Tmp() {
-        for (void *q : p) (void)hipFree(q);
-    }
-};
-
 #define TR_TRY(x)                       \
     do {                                \
         const hipError_t e_ = (x);      \
@@ -116,7 +102,7 @@ int bits_for(uint32_t v) {   // 0 for v == 0
 
 hipError_t transpose_body(const int32_t *rp, const int32_t *col, const float *val, int64_t n_rows, int64_t n_cols,
                           int64_t nnz, int32_t *t_rp, int32_t *t_col, float *t_val, hipStream_t s) {
-    Tmp t;
+    DevScratch t;
     if (t_rp) {   // (null with t_col: only the values' new order is wanted)
         int32_t *cnt = nullptr;
         TR_TRY(t.alloc(&cnt, n_cols + 1));
@@ -174,7 +160,7 @@ hipError_t transpose_ids_device(const int32_t *rp, const int32_t *col, const uin
     if (nnz <= 0) return hipSuccess;
     hipError_t e = hipSuccess;
     {
-        Tmp t;
+        DevScratch t;
         uint32_t *wide = nullptr, *t_wide = nullptr;
         e = t.alloc(&wide, nnz);
         if (e == hipSuccess) e = t.alloc(&t_wide, nnz);
@@ -200,7 +186,7 @@ hipError_t transpose_terms_device(const int32_t *rp, const int32_t *col, int64_t
     if (nnz <= 0) return hipSuccess;
     hipError_t e = hipSuccess;
     {
-        Tmp t;
+        DevScratch t;
         uint32_t *idx = nullptr;
         e = t.alloc(&idx, nnz);
         if (e == hipSuccess) {

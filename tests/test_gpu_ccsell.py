@@ -103,7 +103,7 @@ def test_config5_columns_auto_ccsell_vs_oracle(sm):
     """BASELINE config 5's slice shape at reduced rows: 2^17 rows x 2^26 global columns,
     16 distinct uniform columns per row (seed 5).  The column-chunked layout (x = 256 MiB,
     64 chunks of 4 MiB; forced here) is bit-identical to the oracle on every row; AUTO
-    (the gather-band kind by its cost model, capi.cpp gather_cost_ok) is bit-identical with
+    (the gather-band kind by its cost model, layouts.cpp gather_cost_ok) is bit-identical with
     one slab and within 1e-6 * sum|terms| with several (slab sums added in slab order)."""
     torch = torch_dev()
     import sparsematrix_amd.synth as synth

@@ -165,6 +165,36 @@ def test_deterministic(sm):
         assert same_bits(M.sddmm_table(Gd, Xd, algo=algo), M.sddmm_table(Gd, Xd, algo=algo))
 
 
+def test_sddmm_table_two_streams(sm):
+    """sddmm_table calls on one matrix from two streams at once: the per-chunk partials belong to
+    the matrix, so the library makes the calls take turns on the device and every result equals
+    its one-stream result bit for bit (three chunks of partials, the last one partial)."""
+    torch = torch_dev()
+    n_rows, n_cols, N, T = 1000, 777, 4, 7
+    rp, ci = pattern(n_rows, n_cols, 5)
+    ids = uniform_ids(ci.size, T)
+    M = sm.SparseMatrix.from_csr_ids(rp, ci, ids, make_table(T), n_cols)
+    pairs = []
+    for k in range(8):
+        G, X, _ = grid_inputs(n_rows, n_cols, ci.size, N, seed=700 + 10 * k)
+        pairs.append((to_dev(G), to_dev(X)))
+    want = [bits(to_host(M.sddmm_table(Gd, Xd))) for Gd, Xd in pairs]   # on the default stream
+    assert any(not np.array_equal(want[0], w) for w in want[1:])
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    outs = [to_dev(np.zeros(T, np.float32)) for _ in pairs]
+    torch.cuda.synchronize()
+    for rep in range(3):
+        for out in outs:
+            out.fill_(1.0)   # (finite: beta = 0 still multiplies)
+        torch.cuda.synchronize()
+        for i, ((Gd, Xd), out) in enumerate(zip(pairs, outs)):
+            with torch.cuda.stream(streams[i % 2]):
+                M.sddmm_table(Gd, Xd, out=out)
+        torch.cuda.synchronize()
+        for i, out in enumerate(outs):
+            assert np.array_equal(bits(to_host(out)), want[i]), (rep, i)
+
+
 def test_alpha_zero_takes_no_operands(sm):
     rp, ci = pattern(300, 257, 6)
     T, ids = 7, uniform_ids(ci.size, 7)
