@@ -459,6 +459,7 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
     SellDev &d = p.sell;
     d.max_len = max_len;
     d.n_long = n_long;
+    const size_t mark = m->mem.mark();
     BD_TRY(m->mem.alloc(&d.d_long_rows, n_long));
     BD_TRY(m->mem.alloc(&d.d_long_ptr, n_long + 1));
     BD_TRY(m->mem.alloc(&d.d_partials, n_parts));
@@ -494,7 +495,7 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
     BD_TRY(hipMemcpyAsync(d.d_off, offs, (size_t)ns * 8, hipMemcpyDeviceToDevice, s));
     BD_TRY(hipStreamSynchronize(s));
     if (ns == 0 || padded >= ((int64_t)1 << 31) - kSellLanes * kSellUnroll) {   // upload_sell declines
-        m->mem.release(d.d_long_rows, d.d_long_ptr, d.d_partials, d.d_off, d.d_len);
+        m->mem.release_since(mark);
         d = SellDev();
         return 0;
     }

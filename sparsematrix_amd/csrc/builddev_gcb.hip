@@ -438,8 +438,8 @@ int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, G
     GK_TRY(hipMemsetAsync(mx, 0, 4, s));
     hipLaunchKernelGGL(gk_cut_kernel, dim3((unsigned)ntile), dim3(kCutThreads), 0, s, tts, scol, srl, window, bstart, nb);
     GK_TRY(hipGetLastError());
-    GK_TRY(m->mem.alloc(&m->plan.xb.d_chunk_start, ntile + 1));
-    tbs = m->plan.xb.d_chunk_start;
+    GK_TRY(m->mem.alloc(&m->plan.gcb.d_tile_band, ntile + 1));
+    tbs = m->plan.gcb.d_tile_band;
     {
         size_t bytes = 0;
         GK_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, nb, tbs, (int)(ntile + 1), s));
@@ -454,21 +454,18 @@ int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, G
     GK_TRY(hipMemcpyAsync(&max_bands, mx, 4, hipMemcpyDeviceToHost, s));
     GK_TRY(hipStreamSynchronize(s));
     // gcb_build's output limits: a tile's bands under 4 GiB of 32-bit byte offsets.
-    if ((int64_t)max_bands * kGcbBandWords * 4 >= ((int64_t)1 << 32) || n_bands <= 0 || n_bands >= INT32_MAX) {
-        m->mem.release(m->plan.xb.d_chunk_start);
-        return 1;
-    }
+    if ((int64_t)max_bands * kGcbBandWords * 4 >= ((int64_t)1 << 32) || n_bands <= 0 || n_bands >= INT32_MAX) return 1;
     int32_t *gstart = nullptr, *gtile = nullptr;
     GK_TRY(tp.alloc(&gstart, n_bands));
     GK_TRY(tp.alloc(&gtile, n_bands));
     hipLaunchKernelGGL(gk_compact_kernel, dim3((unsigned)std::min<int64_t>(ntile, 1 << 16)), dim3(256), 0, s, ntile,
                        tts, tbs, bstart, gstart, gtile);
     GK_TRY(hipGetLastError());
-    XbandDev &d = m->plan.xb;
+    GcbDev &d = m->plan.gcb;
     GK_TRY(m->mem.alloc(&d.d_band_clo, n_bands));
-    GK_TRY(m->mem.alloc(&d.d_word, (int64_t)n_bands * kGcbBandWords));
+    GK_TRY(m->mem.alloc(&d.d_ent, (int64_t)n_bands * kGcbBandWords));
     hipLaunchKernelGGL(gk_emit_kernel, dim3((unsigned)n_bands), dim3(kCutThreads), 0, s, (int64_t)n_bands, tts, gstart,
-                       gtile, scol, srl, sval, d.d_band_clo, d.d_word, flag);
+                       gtile, scol, srl, sval, d.d_band_clo, d.d_ent, flag);
     GK_TRY(hipGetLastError());
     GK_TRY(hipMemcpyAsync(&fl, flag, 4, hipMemcpyDeviceToHost, s));
     GK_TRY(hipStreamSynchronize(s));

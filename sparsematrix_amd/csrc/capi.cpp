@@ -622,8 +622,8 @@ sm_status sm_get_info(const sm_matrix *m, sm_info *info) {
 
 sm_status sm_debug_seed_handoff(sm_matrix *m, uint64_t started) {
     if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
-    const XbandDev &xb = m->plan.xb;
-    if (xb.n_blocks <= 0 || (xb.kind != kXbBand2 && xb.kind != kXbCband) || xb.n_slabs < 2 || !xb.d_tickets)
+    const Band2Dev &xb = m->plan.b2;
+    if (xb.n_blocks <= 0 || xb.n_slabs < 2 || !xb.d_tickets)
         return fail(SM_ERR_NOT_SUPPORTED, "no multi-slab band2/cband layout");
     if (started % (uint64_t)xb.n_slabs != 0)
         return fail(SM_ERR_NOT_SUPPORTED, "started must be a multiple of the slab count");
@@ -654,20 +654,17 @@ sm_status sm_get_info_ex(const sm_matrix *m, sm_info *out, size_t info_bytes) {
     info->n_tiles = m->plan.n_tiles;
     info->n_long_rows = m->plan.n_long;
     info->max_row_nnz = m->plan.max_row_nnz;
-    info->has_xband = m->plan.xb.n_blocks > 0 ? m->plan.xb.kind : 0;
-    info->xband_blocks = m->plan.xb.n_blocks;
-    info->xband_bands = m->plan.xb.n_bands;
-    info->xband_slabs = m->plan.xb.n_blocks > 0 ? m->plan.xb.n_slabs : 0;
-    info->xband_block_rows = m->plan.xb.block_rows;
-    info->xband_slab_cols =
-        m->plan.xb.n_blocks == 0 ? 0
-        : m->plan.xb.kind == kXbBand2 || m->plan.xb.kind == kXbCband || m->plan.xb.kind == kXbGcb
-            ? m->plan.xb.slab_bands   // band2 / cband / gcb keep slab columns there
-        : (int32_t)std::min<int64_t>((int64_t)m->plan.xb.slab_bands * m->plan.xb.band_cols, INT32_MAX);
-    info->xband_slab0_cols = m->plan.xb.slab0_cols > 0 ? m->plan.xb.slab0_cols : info->xband_slab_cols;
+    if (const BandTiles *b = m->plan.band()) {
+        info->has_xband = b->kind;
+        info->xband_blocks = b->n_blocks;
+        info->xband_bands = b->n_bands;
+        info->xband_slabs = b->n_slabs;
+        info->xband_block_rows = b->block_rows;
+    }
+    info->xband_slab_cols = m->plan.band_slab_cols();
+    info->xband_slab0_cols = m->plan.band_slab0_cols();
     info->merge_stage = m->plan.d_mstage_w ? 1 : 0;
-    info->xband_beta_last = SM_B2_BL && m->plan.xb.n_blocks > 0 && m->plan.xb.n_slabs > 1 &&
-                            (m->plan.xb.kind == kXbBand2 || m->plan.xb.kind == kXbCband);
+    info->xband_beta_last = SM_B2_BL && m->plan.b2.n_blocks > 0 && m->plan.b2.n_slabs > 1;
     info->device_bytes = m->mem.bytes;
     info->updatable = m->opts.updatable ? 1 : 0;
     info->table_updatable = m->opts.table_updatable ? 1 : 0;
@@ -700,17 +697,17 @@ sm_status sm_layout_digest(const sm_matrix *m, uint64_t digest[4]) {
         if ((st = fnv_dev(f, p.d_rcol, m->nnz)) != SM_OK) return st;
         digest[0] = f.h;
     }
-    const XbandDev &xb = p.xb;
-    if (xb.kind == kXbGcb && xb.n_blocks > 0) {   // gathered chunk bands (gcb.h)
-        const int64_t ntile = (int64_t)xb.n_blocks * xb.n_slabs;
+    const GcbDev &gb = p.gcb;
+    if (gb.n_blocks > 0) {   // gathered chunk bands (gcb.h)
+        const int64_t ntile = (int64_t)gb.n_blocks * gb.n_slabs;
         Fnv f;
-        const int32_t geo[5] = {xb.block_rows, xb.band_cols, xb.n_blocks, xb.n_slabs, xb.slab_bands};
+        const int32_t geo[5] = {gb.block_rows, gb.window, gb.n_blocks, gb.n_slabs, gb.slab_cols};
         f.add(geo, sizeof(geo));
-        if ((st = fnv_dev(f, xb.d_chunk_start, ntile + 1)) != SM_OK) return st;
-        if ((st = fnv_dev(f, xb.d_band_clo, xb.n_bands)) != SM_OK) return st;
+        if ((st = fnv_dev(f, gb.d_tile_band, ntile + 1)) != SM_OK) return st;
+        if ((st = fnv_dev(f, gb.d_band_clo, gb.n_bands)) != SM_OK) return st;
         digest[1] = f.h;
         Fnv w;
-        if ((st = fnv_dev(w, xb.d_word, (int64_t)xb.n_bands * kGcbBandWords)) != SM_OK) return st;
+        if ((st = fnv_dev(w, gb.d_ent, (int64_t)gb.n_bands * kGcbBandWords)) != SM_OK) return st;
         digest[2] = w.h;
     }
     const SellDev &d = p.sell;
@@ -801,12 +798,11 @@ sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t table_si
     m->table_size = er.table_size;
     m->table = std::move(er.table);
     adopt_ref_stream(m, std::move(er));
+    const size_t mark = m->mem.mark();
     const sm_status st = upload_native(m);
     if (st != SM_OK) {   // no half-built encoding -- a retry starts over
-        NativeDev &n = m->plan.nat;
-        m->mem.release(n.d_pos, n.d_val, n.d_beg, n.d_end, n.d_col, n.d_table, n.d_pbatch, n.d_bmeta, n.d_boff,
-                       n.d_lists, n.d_hdr);
-        n = NativeDev{};
+        m->mem.release_since(mark);
+        m->plan.nat = NativeDev{};
         m->has_ref = false;
         m->table_size = 0;
         for (auto *v : {&m->pos, &m->val}) std::vector<uint8_t>().swap(*v);
@@ -897,12 +893,8 @@ static hipError_t launch_spmv_algo(const sm_matrix *m, int ai, float alpha, cons
             e = launch_spmv_sweep(m->plan.sw, n, (int32_t)m->n_cols, x, y, alpha, beta, s);
             break;
         }
-        if (m->plan.xb.n_blocks > 0 && ((uintptr_t)x % 16) == 0) {
-            e = m->plan.xb.kind == kXbBand2 || m->plan.xb.kind == kXbCband
-                    ? launch_spmv_band2(m->plan.xb, n, (int32_t)m->n_cols, x, y, alpha, beta, s)
-                : m->plan.xb.kind == kXbGcb
-                    ? launch_spmv_gcb(m->plan.xb, n, (int32_t)m->n_cols, x, y, alpha, beta, s)
-                    : launch_spmv_xband(m->plan.xb, n, (int32_t)m->n_cols, x, y, alpha, beta, s);
+        if (m->plan.band() && ((uintptr_t)x % 16) == 0) {
+            e = launch_spmv_band(m->plan, n, (int32_t)m->n_cols, x, y, alpha, beta, s);
             break;
         }
         // fall through: no band layout (or unaligned x) -> sell or stream kernel
@@ -968,6 +960,17 @@ static hipError_t launch_spmv_algo(const sm_matrix *m, int ai, float alpha, cons
     return e;
 }
 
+// Whether launch_spmv_algo(m, ai, ...) takes a turn on the matrix's SpMV scratch (sm_internal.h):
+// SpMVs that do run one after the other on the device, whatever stream or thread issues them.
+// Deliberately a superset of what the route launches: any built layout that has scratch owned
+// by the matrix counts (slab partials, the relabeled x, long-row partials), used by `ai` or not.
+static bool spmv_takes_turn(const Plan &pl, int ai) {
+    if (ai == SM_ALGO_MERGE) return true;
+    if (ai == SM_ALGO_PARITY || ai == SM_ALGO_VECTOR) return false;
+    return pl.band_slabs() > 1 || pl.n_relabel > 0 || (pl.hot.n_blocks > 0 && pl.hot.n_slabs > 1) ||
+           pl.sell.n_long > 0 || pl.n_long > 0;
+}
+
 sm_status sm_spmv(const sm_matrix *m, float alpha, const float *x, float beta, float *y,
                   sm_algo algo, sm_stream stream) {
     if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
@@ -997,15 +1000,8 @@ sm_status sm_spmv(const sm_matrix *m, float alpha, const float *x, float beta, f
     const int ai = algo == SM_ALGO_EXACT ? exact_algo(m, ((uintptr_t)x % 16) == 0) : (int)algo;
     if ((ai < SM_ALGO_AUTO || ai > SM_ALGO_SELL) && ai != kAlgoExactSell && ai != SM_ALGO_MERGE)
         return fail(SM_ERR_INVALID_ARG, "unknown algo %d", (int)algo);
-    // The matrix's SpMV scratch (sm_internal.h): SpMVs that use it run one after the
-    // other on the device, whatever stream or thread issues them.
-    const Plan &pl = m->plan;
-    const bool scratch = ai == SM_ALGO_MERGE ||
-                         (ai != SM_ALGO_PARITY && ai != SM_ALGO_VECTOR &&
-                          ((pl.xb.n_blocks > 0 && pl.xb.n_slabs > 1) || pl.n_relabel > 0 ||
-                           (pl.hot.n_blocks > 0 && pl.hot.n_slabs > 1) ||
-                           pl.sell.n_long > 0 || pl.n_long > 0));
-    e = with_turn(m->scratch_turn, s, scratch, [&] { return launch_spmv_algo(m, ai, alpha, x, beta, y, s); });
+    e = with_turn(m->scratch_turn, s, spmv_takes_turn(m->plan, ai),
+                  [&] { return launch_spmv_algo(m, ai, alpha, x, beta, y, s); });
     e = after_launch(e, s, "sm_spmv");
     return e == hipSuccess ? SM_OK : hip_fail(e, "sm_spmv launch");
 }
@@ -1097,12 +1093,9 @@ static sm_status update_values(sm_matrix *m, bool axpy, float a, const float *d_
     const Plan &p = m->plan;
     hipError_t e = launch_values_csr(m->nnz, axpy, a, d_in, order == SM_VALUES_SOURCE ? m->d_src_term : nullptr,
                                      m->d_val, s);
-    if (e == hipSuccess && p.xb.d_term) {
-        if (p.xb.kind == kXbBand2 || p.xb.kind == kXbGcb)
-            e = launch_refresh_entry(p.xb.n_term, p.xb.d_term, m->d_val, p.xb.d_word, s);
-        else
-            e = launch_refresh_plain(p.xb.n_term, p.xb.d_term, m->d_val, p.xb.d_val, s);
-    }
+    if (e == hipSuccess && p.xb.d_term) e = launch_refresh_plain(p.xb.n_term, p.xb.d_term, m->d_val, p.xb.d_val, s);
+    if (e == hipSuccess && p.b2.d_term) e = launch_refresh_entry(p.b2.n_term, p.b2.d_term, m->d_val, p.b2.d_ent, s);
+    if (e == hipSuccess && p.gcb.d_term) e = launch_refresh_entry(p.gcb.n_term, p.gcb.d_term, m->d_val, p.gcb.d_ent, s);
     for (const SellDev *d : {&p.sell, &p.xsell})
         if (e == hipSuccess && d->d_term) e = launch_refresh_plain(d->n_term, d->d_term, m->d_val, d->d_val, s);
     if (e == hipSuccess && p.cc.d_term) e = launch_refresh_plain(p.cc.n_term, p.cc.d_term, m->d_val, p.cc.d_val, s);
@@ -1185,7 +1178,7 @@ static sm_status update_table(sm_matrix *m, bool axpy, float a, const float *d_i
         dst.p[dst.count] = tab;
         dst.n[dst.count++] = n;
     };
-    if (p.xb.n_blocks > 0) add(p.xb.d_table, 256);
+    if (p.b2.n_blocks > 0) add(p.b2.d_table, 256);
     if (p.sell.n_slices > 0) add(p.sell.d_table, p.sell.table_size);
     if (p.xsell.n_slices > 0) add(p.xsell.d_table, p.xsell.table_size);
     if (p.cc.n_slices > 0) add(p.cc.d_table, 256);

@@ -2,7 +2,8 @@
 // multi.cpp's gather buffers, the C++ shim's operands and the growth of the AddMatMat
 // workspace).  Two owners:
 //   DevMem      what a matrix keeps: every buffer is recorded with its size, counted in `bytes`
-//               (sm_info.device_bytes) and freed with the matrix; release() drops one early.
+//               (sm_info.device_bytes) and freed with the matrix; release() drops one early,
+//               release_since() everything a dropped layout allocated.
 //   DevScratch  what a call needs until it returns: freed at scope end.
 // Both hand out raw typed pointers, so the launchers and the *Dev structs stay plain data.
 #pragma once
@@ -47,12 +48,20 @@ struct DevMem {
         ((p = nullptr), ...);
     }
 
-    // The caller makes the buffers' device current.
-    void release_all() {
-        for (const Buf &b : bufs) (void)hipFree(b.p);
-        bufs.clear();
-        bytes = 0;
+    // Undo for a layout that is tried and then dropped: release_since(mark()) frees every buffer
+    // allocated after the mark (bufs is in allocation order) and takes its bytes off the count.
+    // The caller resets the descriptor that held the pointers, and releases no buffer from before
+    // the mark in between (that would shift it).
+    size_t mark() const { return bufs.size(); }
+    void release_since(size_t mark) {
+        for (; bufs.size() > mark; bufs.pop_back()) {
+            (void)hipFree(bufs.back().p);
+            bytes -= bufs.back().bytes;
+        }
     }
+
+    // The caller makes the buffers' device current.
+    void release_all() { release_since(0); }
 
 private:
     void release_one(void *q) {

@@ -556,11 +556,11 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
 #ifdef SM_DEV
 // Development read-out of PROF 1 / 2 (tools/cband_prof.py).
 template <int GEO>
-hipError_t launch_prof(int prof, dim3 grid, hipStream_t s, const XbandDev &xb, int32_t n_rows, int32_t n_cols,
+hipError_t launch_prof(int prof, dim3 grid, hipStream_t s, const Band2Dev &xb, int32_t n_rows, int32_t n_cols,
                        const float *x, float *y, float alpha, float beta) {
 #define SM_B2P(P)                                                                                   \
     hipLaunchKernelGGL((spmv_band2_kernel<true, GEO, P>), grid, dim3(kB2Threads), 0, s, n_rows, n_cols, \
-                       xb.block_rows, xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word,          \
+                       xb.block_rows, xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent,          \
                        xb.d_table, xb.table_size, x, y, xb.d_partials, xb.d_tickets, alpha, beta)
     if (prof == 1) {
         if (GEO != 4) return hipErrorInvalidValue;
@@ -634,14 +634,14 @@ hipError_t launch_prof(int prof, dim3 grid, hipStream_t s, const XbandDev &xb, i
 
 }  // namespace
 
-hipError_t launch_spmv_band2(const XbandDev &xb, int32_t n_rows, int32_t n_cols, const float *x,
+hipError_t launch_spmv_band2(const Band2Dev &xb, int32_t n_rows, int32_t n_cols, const float *x,
                              float *y, float alpha, float beta, hipStream_t s) {
     if (xb.n_blocks <= 0) return hipSuccess;
     const bool cb = xb.kind == kXbCband;
-    const bool dma3 = xb.band_cols == kB2Dma3Cb.window;   // cband or band2 entries
+    const bool dma3 = xb.window == kB2Dma3Cb.window;   // cband or band2 entries
     const B2Geom g = dma3 ? (cb ? kB2Dma3Cb : kB2Dma3B2) : kB2Wide;
-    if ((xb.kind != kXbBand2 && !cb) || xb.n_slabs < 1 || xb.block_rows > g.block_rows ||
-        xb.band_cols != g.window || !xb.d_chunk_start || !xb.d_band_clo || (xb.n_bands > 0 && !xb.d_word) ||
+    if (xb.n_slabs < 1 || xb.block_rows > g.block_rows ||
+        xb.window != g.window || !xb.d_tile_band || !xb.d_band_clo || (xb.n_bands > 0 && !xb.d_ent) ||
         (cb && (!xb.d_table || xb.table_size < 0 || xb.table_size > (int32_t)kCbDummyId)) ||
         (xb.n_slabs > 1 && (!xb.d_partials || !xb.d_tickets)))
         return hipErrorInvalidValue;
@@ -659,7 +659,7 @@ hipError_t launch_spmv_band2(const XbandDev &xb, int32_t n_rows, int32_t n_cols,
 #endif
 #define SM_B2(C, T)                                                                                 \
     hipLaunchKernelGGL((spmv_band2_kernel<C, T, 0>), grid, dim3(kB2Threads), 0, s, n_rows, n_cols,    \
-                       xb.block_rows, xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word,          \
+                       xb.block_rows, xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent,          \
                        xb.d_table, xb.table_size, x, y, xb.d_partials, xb.d_tickets, alpha, beta)
     if (dma3) {
         if (cb) SM_B2(true, 4); else SM_B2(false, 4);

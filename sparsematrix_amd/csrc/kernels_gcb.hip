@@ -250,17 +250,17 @@ __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
 
 }  // namespace
 
-hipError_t launch_spmv_gcb(const XbandDev &xb, int32_t n_rows, int32_t n_cols, const float *x, float *y,
+hipError_t launch_spmv_gcb(const GcbDev &xb, int32_t n_rows, int32_t n_cols, const float *x, float *y,
                            float alpha, float beta, hipStream_t s) {
     if (xb.n_blocks <= 0) return hipSuccess;
-    if (xb.kind != kXbGcb || xb.n_slabs < 1 || !xb.d_chunk_start || !xb.d_band_clo ||
-        (xb.n_bands > 0 && !xb.d_word) || (xb.n_slabs > 1 && (!xb.d_partials || !xb.d_tickets)) ||
+    if (xb.n_slabs < 1 || !xb.d_tile_band || !xb.d_band_clo ||
+        (xb.n_bands > 0 && !xb.d_ent) || (xb.n_slabs > 1 && (!xb.d_partials || !xb.d_tickets)) ||
         xb.block_rows > (1 << 15))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)((int64_t)xb.n_blocks * xb.n_slabs)), block(kGcbThreads);
 #define SM_GCB(RL, ER, GA)                                                                         \
     hipLaunchKernelGGL((spmv_gcb_kernel<RL, ER, GA>), grid, block, 0, s, n_rows, n_cols, xb.block_rows, \
-                       xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word, x, y, xb.d_partials,  \
+                       xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,  \
                        xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack)
     int look = 0;
     int32_t *pace = nullptr;
@@ -272,10 +272,10 @@ hipError_t launch_spmv_gcb(const XbandDev &xb, int32_t n_rows, int32_t n_cols, c
         const int a = atoi(e);
 #define SM_GCBX(A)                                                                                 \
     if (tall) hipLaunchKernelGGL((spmv_gcb_kernel<15, 6, 2, 0, false, A>), grid, block, 0, s, n_rows, n_cols,    \
-                                 xb.block_rows, xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word, x, y,  \
+                                 xb.block_rows, xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y,  \
                                  xb.d_partials, xb.d_tickets, alpha, beta, nullptr, 0, 0);                   \
     else hipLaunchKernelGGL((spmv_gcb_kernel<14, 6, 2, 0, false, A>), grid, block, 0, s, n_rows, n_cols,         \
-                            xb.block_rows, xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word, x, y,       \
+                            xb.block_rows, xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y,       \
                             xb.d_partials, xb.d_tickets, alpha, beta, nullptr, 0, 0)
         switch (a) {
         case 1: SM_GCBX(1); break;
@@ -295,10 +295,10 @@ hipError_t launch_spmv_gcb(const XbandDev &xb, int32_t n_rows, int32_t n_cols, c
         const int abl = atoi(e);
 #define SM_GCBA(A)                                                                                    \
     if (tall) hipLaunchKernelGGL((spmv_gcb_kernel<15, 6, 2, A>), grid, block, 0, s, n_rows, n_cols, xb.block_rows, \
-                                 xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word, x, y, xb.d_partials,  \
+                                 xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,  \
                                  xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack);            \
     else hipLaunchKernelGGL((spmv_gcb_kernel<14, 6, 2, A>), grid, block, 0, s, n_rows, n_cols, xb.block_rows, \
-                            xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word, x, y, xb.d_partials,  \
+                            xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,  \
                             xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack)
         switch (abl) {
         case 1: SM_GCBA(1); break;
@@ -315,11 +315,11 @@ hipError_t launch_spmv_gcb(const XbandDev &xb, int32_t n_rows, int32_t n_cols, c
     if (pace) {
         if (tall)
             hipLaunchKernelGGL((spmv_gcb_kernel<15, 6, 2, 0, true>), grid, block, 0, s, n_rows, n_cols, xb.block_rows,
-                               xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word, x, y, xb.d_partials,
+                               xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,
                                xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack);
         else
             hipLaunchKernelGGL((spmv_gcb_kernel<14, 6, 2, 0, true>), grid, block, 0, s, n_rows, n_cols, xb.block_rows,
-                               xb.n_slabs, xb.d_chunk_start, xb.d_band_clo, xb.d_word, x, y, xb.d_partials,
+                               xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,
                                xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack);
         return hipGetLastError();
     }

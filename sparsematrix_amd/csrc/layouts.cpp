@@ -224,6 +224,17 @@ static bool codebook_source(const sm_matrix *m, const float *val, int64_t nnz, s
     return true;
 }
 
+// The slab scratch of a band layout whose n_blocks and n_slabs are set: `row_sets` sets of n_rows
+// partial sums, each set 16-byte aligned, and the hand-off control words, 4 per block and zero
+// between SpMVs.  Nothing for one slab.
+static sm_status alloc_slab_scratch(sm_matrix *m, BandTiles &d, int64_t n_rows, int64_t row_sets) {
+    if (d.n_slabs <= 1) return SM_OK;
+    SM_TRY_HIP(m->mem.alloc(&d.d_partials, row_sets * ((n_rows + 3) & ~(int64_t)3)));
+    SM_TRY_HIP(m->mem.alloc(&d.d_tickets, 4 * (int64_t)d.n_blocks));
+    SM_TRY_HIP(hipMemset(d.d_tickets, 0, (size_t)d.n_blocks * 4 * sizeof(int32_t)));
+    return SM_OK;
+}
+
 // Balanced-band layout (band2.cpp, kernels_band2.hip): slabs so there are about
 // kXbTargetTiles tiles of <= 16K rows.  kind cband: 4-byte codebook words when the
 // values take <= 255 distinct bit patterns, else (or kind band2) 8-byte entries.
@@ -233,7 +244,7 @@ static bool codebook_source(const sm_matrix *m, const float *val, int64_t nnz, s
 // stages x -- config 2 34.0-34.6 vs 36.9-37.1 us for the wide geometry with codebook words,
 // 37.9-38.0 vs 38.6-38.7 with 8-byte entries), 4 = dma3, 6 = wide.  dma3
 // bands that would be < 70 % full fall back to wide.
-static sm_status build_band2(sm_matrix *m, XbandDev &d, int64_t n_rows, int64_t n_cols, int64_t nnz,
+static sm_status build_band2(sm_matrix *m, Band2Dev &d, int64_t n_rows, int64_t n_cols, int64_t nnz,
                              const int32_t *rp, const int32_t *col, const float *val, XbKind kind,
                              int32_t geo_opt, int32_t slabs, bool forced, int32_t slab0_permille = 1000) {
     const bool dma3 = geo_opt != 6;
@@ -269,55 +280,35 @@ static sm_status build_band2(sm_matrix *m, XbandDev &d, int64_t n_rows, int64_t 
     std::vector<uint8_t>().swap(ids);
     const int64_t band_words = (int64_t)(cb ? 64 : 128) * g.chunks();
     const int64_t ntile = (int64_t)bh.n_blocks * bh.n_slabs;
-    SM_TRY_HIP(m->mem.alloc(&d.d_chunk_start, ntile + 1));
+    d.kind = cb ? kXbCband : kXbBand2;
+    d.block_rows = bh.block_rows;
+    d.n_blocks = bh.n_blocks;
+    d.n_bands = (int32_t)std::min<int64_t>(bh.n_bands, INT32_MAX);
+    d.n_slabs = bh.n_slabs;
+    d.window = g.window;
+    d.slab_cols = bh.slab_cols;
+    d.slab0_cols = bh.slab0_cols;
+    SM_TRY_HIP(m->mem.alloc(&d.d_tile_band, ntile + 1));
     SM_TRY_HIP(m->mem.alloc(&d.d_band_clo, std::max<int64_t>(1, bh.n_bands)));
-    SM_TRY_HIP(m->mem.alloc(&d.d_word, std::max<int64_t>(1, bh.n_bands * band_words)));
+    SM_TRY_HIP(m->mem.alloc(&d.d_ent, std::max<int64_t>(1, bh.n_bands * band_words)));
     if (cb) {
         SM_TRY_HIP(dev_upload_table(m->mem, &d.d_table, table.data(), (int32_t)table.size()));
         d.table_size = (int32_t)table.size();
     }
-    if (bh.n_slabs > 1) {
-        const int64_t ps = (n_rows + 3) & ~(int64_t)3;   // 16-byte aligned partial rows
-        // One partial per slab: the beta-last hand-off (kernels_band2.hip SM_B2_BL) publishes
-        // slab 0's sums too (the other form writes them into y and leaves the last one unused).
-        SM_TRY_HIP(m->mem.alloc(&d.d_partials, (int64_t)bh.n_slabs * ps));
-        SM_TRY_HIP(m->mem.alloc(&d.d_tickets, 4 * (int64_t)bh.n_blocks));
-        SM_TRY_HIP(hipMemset(d.d_tickets, 0, (size_t)bh.n_blocks * 4 * sizeof(int32_t)));
-    }
-    SM_TRY_HIP(hipMemcpy(d.d_chunk_start, bh.tile_band_start.data(), (size_t)(ntile + 1) * 4,
+    // One row set per slab: the beta-last hand-off (kernels_band2.hip SM_B2_BL) publishes slab 0's
+    // sums too (the other form writes them into y and leaves the last one unused).
+    if (const sm_status sts = alloc_slab_scratch(m, d, n_rows, bh.n_slabs)) return sts;
+    SM_TRY_HIP(hipMemcpy(d.d_tile_band, bh.tile_band_start.data(), (size_t)(ntile + 1) * 4,
                          hipMemcpyHostToDevice));
     if (bh.n_bands > 0) {
         SM_TRY_HIP(hipMemcpy(d.d_band_clo, bh.band_clo.data(), (size_t)bh.n_bands * 4,
                              hipMemcpyHostToDevice));
-        SM_TRY_HIP(hipMemcpy(d.d_word, bh.ent.data(), (size_t)(bh.n_bands * band_words) * 4,
+        SM_TRY_HIP(hipMemcpy(d.d_ent, bh.ent.data(), (size_t)(bh.n_bands * band_words) * 4,
                              hipMemcpyHostToDevice));
     }
     if (const sm_status stm = upload_term_map(m, bh.term, &d.d_term)) return stm;
     d.n_term = (int64_t)bh.term.size() / 2;
-    d.kind = cb ? kXbCband : kXbBand2;
-    d.threads = 1024;
-    d.block_rows = bh.block_rows;
-    d.band_cols = g.window;
-    d.n_bands = (int32_t)std::min<int64_t>(bh.n_bands, INT32_MAX);
-    d.n_slabs = bh.n_slabs;
-    d.slab_bands = bh.slab_cols;
-    d.slab0_cols = bh.slab0_cols;
-    d.n_chunks = bh.n_bands * g.chunks();
-    d.max_chunks_per_band = bh.max_bands_per_tile;
-    d.n_blocks = bh.n_blocks;
     return SM_OK;
-}
-
-static sm_status upload_band2(sm_matrix *m, const int32_t *rp, const int32_t *col,
-                              const float *val, XbKind kind) {
-    // Geometry: band_tall (xband.h B2Geom, build_band2).
-    // Slab 0's tile loads and scales y (64 KiB per 16K-row block from HBM) before its first
-    // band: on config 2 its band loop ended 1.5-2.3 us after the other slabs' (per-tile
-    // timeline, profiles/r05_dma3_tile_timeline_dump.txt).  Narrower slab-0 tiles did not
-    // shorten the kernel (kB2Slab0Permille), so AUTO keeps even slabs; the option stays.
-    const int32_t p0 = m->opts.band_slab0_permille > 0 ? m->opts.band_slab0_permille : kB2Slab0Permille;
-    return build_band2(m, m->plan.xb, m->n_rows, m->n_cols, m->nnz, rp, col, val, kind,
-                       m->opts.band_tall, m->opts.band_slabs, kind_forced(m), p0);
 }
 
 // Gathered chunk bands (gcb.h, kernels_gcb.hip): 32K-row tiles where the rows make at
@@ -329,31 +320,23 @@ static void gcb_geometry(const sm_matrix *m, int &rows_log2, int32_t &slabs) {
     if (m->opts.band_slabs > 0) slabs = m->opts.band_slabs;
 }
 
-// The rest of a built gcb layout (its bands already in d_chunk_start / d_band_clo / d_word):
-// slab partials, hand-off and pacing words, the geometry.
+// The rest of a built gcb layout (its bands already in d_tile_band / d_band_clo / d_ent):
+// the geometry, slab partials, hand-off and pacing words.
 static sm_status gcb_finish(sm_matrix *m, const GcbHost &gh) {
-    XbandDev &d = m->plan.xb;
-    if (gh.n_slabs > 1) {
-        const int64_t ps = (m->n_rows + 3) & ~(int64_t)3;   // 16-byte aligned partial rows
-        SM_TRY_HIP(m->mem.alloc(&d.d_partials, (int64_t)(gh.n_slabs - 1) * ps));
-        SM_TRY_HIP(m->mem.alloc(&d.d_tickets, 4 * (int64_t)gh.n_blocks));
-        SM_TRY_HIP(hipMemset(d.d_tickets, 0, (size_t)gh.n_blocks * 4 * sizeof(int32_t)));
-    }
+    GcbDev &d = m->plan.gcb;
+    d.kind = kXbGcb;
+    d.block_rows = gh.block_rows;
+    d.n_blocks = gh.n_blocks;
+    d.n_bands = (int32_t)std::min<int64_t>(gh.n_bands, INT32_MAX);
+    d.n_slabs = gh.n_slabs;
+    d.window = gh.window;
+    d.slab_cols = gh.slab_cols;
+    if (const sm_status sts = alloc_slab_scratch(m, d, m->n_rows, gh.n_slabs - 1)) return sts;
     // Column pacing (kernels_gcb.hip): per dispatch group, a started count and one arrival
     // count per 2^18-column checkpoint, monotonic across launches.
     d.pace_k = (int32_t)((m->n_cols + kGcbMaxWindow - 1) / kGcbMaxWindow);
     SM_TRY_HIP(m->mem.alloc(&d.d_pace, 8 * (1 + (int64_t)d.pace_k)));
     SM_TRY_HIP(hipMemset(d.d_pace, 0, (size_t)8 * (1 + d.pace_k) * sizeof(int32_t)));
-    d.kind = kXbGcb;
-    d.threads = 1024;
-    d.block_rows = gh.block_rows;
-    d.band_cols = gh.window;
-    d.n_bands = (int32_t)std::min<int64_t>(gh.n_bands, INT32_MAX);
-    d.n_slabs = gh.n_slabs;
-    d.slab_bands = gh.slab_cols;
-    d.n_chunks = gh.n_bands * kGcbChunks;
-    d.max_chunks_per_band = gh.max_bands_per_tile;
-    d.n_blocks = gh.n_blocks;
     return SM_OK;
 }
 
@@ -364,16 +347,16 @@ static sm_status upload_gcb(sm_matrix *m, const int32_t *rp, const int32_t *col,
     GcbHost gh;
     if (!gcb_build(rp, col, val, m->n_rows, m->n_cols, rows_log2, slabs, kGcbMaxWindow, gh, m->opts.updatable != 0))
         return SM_OK;
-    XbandDev &d = m->plan.xb;
+    GcbDev &d = m->plan.gcb;
     const int64_t ntile = (int64_t)gh.n_blocks * gh.n_slabs;
-    SM_TRY_HIP(m->mem.alloc(&d.d_chunk_start, ntile + 1));
+    SM_TRY_HIP(m->mem.alloc(&d.d_tile_band, ntile + 1));
     SM_TRY_HIP(m->mem.alloc(&d.d_band_clo, std::max<int64_t>(1, gh.n_bands)));
-    SM_TRY_HIP(m->mem.alloc(&d.d_word, std::max<int64_t>(1, gh.n_bands * kGcbBandWords)));
-    SM_TRY_HIP(hipMemcpy(d.d_chunk_start, gh.tile_band_start.data(), (size_t)(ntile + 1) * 4,
+    SM_TRY_HIP(m->mem.alloc(&d.d_ent, std::max<int64_t>(1, gh.n_bands * kGcbBandWords)));
+    SM_TRY_HIP(hipMemcpy(d.d_tile_band, gh.tile_band_start.data(), (size_t)(ntile + 1) * 4,
                          hipMemcpyHostToDevice));
     if (gh.n_bands > 0) {
         SM_TRY_HIP(hipMemcpy(d.d_band_clo, gh.band_clo.data(), (size_t)gh.n_bands * 4, hipMemcpyHostToDevice));
-        SM_TRY_HIP(hipMemcpy(d.d_word, gh.ent.data(), (size_t)gh.n_bands * kGcbBandWords * 4,
+        SM_TRY_HIP(hipMemcpy(d.d_ent, gh.ent.data(), (size_t)gh.n_bands * kGcbBandWords * 4,
                              hipMemcpyHostToDevice));
     }
     if (const sm_status stm = upload_term_map(m, gh.term, &d.d_term)) return stm;
@@ -385,8 +368,15 @@ sm_status upload_xband(sm_matrix *m, const int32_t *rp, const int32_t *col, cons
                        XbKind kind) {
     if (kind == kXbGcb) return upload_gcb(m, rp, col, val);
     if (kind == kXbBand2 || kind == kXbCband) {
-        const sm_status st = upload_band2(m, rp, col, val, kind);
-        if (st == SM_OK && m->plan.xb.n_blocks == 0 && !kind_forced(m) && !m->opts.table_updatable)
+        // Geometry: band_tall (xband.h B2Geom, build_band2).
+        // Slab 0's tile loads and scales y (64 KiB per 16K-row block from HBM) before its first
+        // band: on config 2 its band loop ended 1.5-2.3 us after the other slabs' (per-tile
+        // timeline, profiles/r05_dma3_tile_timeline_dump.txt).  Narrower slab-0 tiles did not
+        // shorten the kernel (kB2Slab0Permille), so AUTO keeps even slabs; the option stays.
+        const int32_t p0 = m->opts.band_slab0_permille > 0 ? m->opts.band_slab0_permille : kB2Slab0Permille;
+        const sm_status st = build_band2(m, m->plan.b2, m->n_rows, m->n_cols, m->nnz, rp, col, val, kind,
+                                         m->opts.band_tall, m->opts.band_slabs, kind_forced(m), p0);
+        if (st == SM_OK && m->plan.b2.n_blocks == 0 && !kind_forced(m) && !m->opts.table_updatable)
             return upload_xband(m, rp, col, val, kXbBlocked);   // declined: blocked kind
         return st;
     }
@@ -405,12 +395,10 @@ sm_status upload_xband(sm_matrix *m, const int32_t *rp, const int32_t *col, cons
     const XbBits bits = kind == kXbExact    ? xb_bits(kXbExactBandLog2, kXbExactRowsLog2)
                         : kind == kXbGather ? xb_bits(gband_log2, kXbGatherRowsLog2)
                                             : xb_bits(kXbBlockedBandLog2, kXbBlockedRowsLog2);
-    const int threads = kXbThreads;
-    const int64_t target_tiles = (int64_t)kXbTargetTiles * (kXbThreads / threads);   // fill the CUs
     XbandHost xh;
     // Register capacity from the waves that hold entries: 12 on the blocked kind
     // (4 loader waves stage x), all 16 on the exact and gather kinds.
-    const int entry_waves = kind == kXbBlocked ? kXbComputeWaves : threads / 64;
+    const int entry_waves = kind == kXbBlocked ? kXbComputeWaves : kXbThreads / 64;
     if (!xband_build(rp, col, val, m->n_rows, m->n_cols, bits, entry_waves, xh,
                      kind == kXbGather, 0, m->opts.updatable != 0)) {
         // The gather kind's wide bands leave 3-4 rank bits: a matrix with longer row
@@ -427,7 +415,7 @@ sm_status upload_xband(sm_matrix *m, const int32_t *rp, const int32_t *col, cons
     int32_t n_slabs = 1;
     if (kind != kXbExact) {
         // At most 64 slabs: the hand-off counts arrivals in 8 bits (kernels_xband.hip).
-        const int64_t want = std::min<int64_t>(64, (target_tiles + xh.n_blocks - 1) / xh.n_blocks);
+        const int64_t want = std::min<int64_t>(64, ((int64_t)kXbTargetTiles + xh.n_blocks - 1) / xh.n_blocks);
         n_slabs = (int32_t)std::max<int64_t>(1, std::min<int64_t>(want, xh.n_bands));
     }
     // Slabs of whole groups of 8 bands (the kernel steps bands 4 or 8 at a time).
@@ -439,25 +427,17 @@ sm_status upload_xband(sm_matrix *m, const int32_t *rp, const int32_t *col, cons
     SM_TRY_HIP(dev_upload(m->mem, &d.d_chunk_start, cs32));
     SM_TRY_HIP(dev_upload(m->mem, &d.d_word, xh.word));
     SM_TRY_HIP(dev_upload(m->mem, &d.d_val, xh.val));
-    if (n_slabs > 1) {
-        const int64_t ps = (m->n_rows + 3) & ~(int64_t)3;   // 16-byte aligned partial rows
-        SM_TRY_HIP(m->mem.alloc(&d.d_partials, (int64_t)(n_slabs - 1) * ps));
-        // Slab hand-off control words (kernels_xband.hip: started, arrive, done, pad).
-        SM_TRY_HIP(m->mem.alloc(&d.d_tickets, 4 * (int64_t)xh.n_blocks));
-        SM_TRY_HIP(hipMemset(d.d_tickets, 0, (size_t)xh.n_blocks * 4 * sizeof(int32_t)));
-    }
-    if (const sm_status stm = upload_term_map(m, xh.term, &d.d_term)) return stm;
-    d.n_term = (int64_t)xh.term.size();
     d.kind = kind;
-    d.threads = threads;
     d.block_rows = xh.block_rows;
-    d.band_cols = xh.band_cols;
+    d.n_blocks = xh.n_blocks;
     d.n_bands = xh.n_bands;
     d.n_slabs = n_slabs;
     d.slab_bands = slab_bands;
-    d.n_chunks = xh.n_chunks;
+    d.band_cols = xh.band_cols;
     d.max_chunks_per_band = xh.max_chunks_per_band;
-    d.n_blocks = xh.n_blocks;
+    if (const sm_status sts = alloc_slab_scratch(m, d, m->n_rows, n_slabs - 1)) return sts;
+    if (const sm_status stm = upload_term_map(m, xh.term, &d.d_term)) return stm;
+    d.n_term = (int64_t)xh.term.size();
     return SM_OK;
 }
 
@@ -471,7 +451,7 @@ bool want_relabel_size(const sm_matrix *m) {
     if (m->opts.relabel == 0) return false;
     if (m->nnz == 0 || m->n_cols == 0) return false;
     if (m->opts.relabel == 1) return true;
-    return m->n_cols >= (1 << 20) && m->nnz >= m->n_cols && m->plan.xb.n_blocks == 0;
+    return m->n_cols >= (1 << 20) && m->nnz >= m->n_cols && !m->plan.band();
 }
 
 sm_status upload_relabel(sm_matrix *m, const int32_t *col) {
@@ -541,7 +521,7 @@ sm_status upload_merge_stage(sm_matrix *m, const int32_t *rp, const int32_t *col
 // reference's order (the stream kernel: rows up to 64).
 bool want_sell(const sm_matrix *m) {
     if (m->opts.sell == 0) return false;
-    return m->nnz > 0 && m->n_rows > 0 && m->plan.xb.n_blocks == 0 && m->plan.cc.n_slices == 0 &&
+    return m->nnz > 0 && m->n_rows > 0 && !m->plan.band() && m->plan.cc.n_slices == 0 &&
            m->plan.sw.n_blocks == 0;
 }
 
@@ -623,7 +603,7 @@ sm_status upload_sell(sm_matrix *m, const int32_t *rp, const int32_t *col, const
 int exact_algo(const sm_matrix *m, bool x16) {
     const Plan &pl = m->plan;
     if (pl.sw.n_blocks > 0) return SM_ALGO_XBAND;                                  // column-swept blocks
-    if (pl.xb.n_blocks > 0 && pl.xb.n_slabs == 1 && x16) return SM_ALGO_XBAND;    // one slab of bands
+    if (pl.band_slabs() == 1 && x16) return SM_ALGO_XBAND;                        // one slab of bands
     if (pl.cc.n_slices > 0) return SM_ALGO_SELL;                                    // column-chunked ELL
     if (pl.sell.n_slices > 0 && pl.sell.n_long == 0 && pl.hot.n_blocks == 0) return SM_ALGO_SELL;
     if (pl.max_row_nnz <= SM_SERIAL_ROW_MAX) return SM_ALGO_STREAM;                // serial rows only
@@ -654,7 +634,7 @@ sm_status upload_exact_sell(sm_matrix *m, const int32_t *rp, const int32_t *col,
 // terms inside one column chunk.  ccsell = 0 / 1 never / always tries it.
 // Column-swept row blocks (sweep.h, kernels_sweep.hip): forced by SM_LAYOUT_SWEEP.
 bool want_sweep(const sm_matrix *m) {
-    if (m->nnz == 0 || m->n_rows == 0 || m->plan.xb.n_blocks > 0) return false;
+    if (m->nnz == 0 || m->n_rows == 0 || m->plan.band()) return false;
     if (m->n_cols >= ((int64_t)1 << 30)) return false;   // 32-bit byte offsets into x
     return m->opts.layout == SM_LAYOUT_SWEEP;
 }
@@ -681,7 +661,7 @@ sm_status upload_sweep(sm_matrix *m, const int32_t *rp, const int32_t *col, cons
 
 bool want_ccsell(const sm_matrix *m) {
     if (m->opts.ccsell == 0 || m->opts.sell == 0) return false;
-    if (m->nnz == 0 || m->n_rows == 0 || m->plan.xb.n_blocks > 0 || m->plan.n_relabel > 0 ||
+    if (m->nnz == 0 || m->n_rows == 0 || m->plan.band() || m->plan.n_relabel > 0 ||
         m->plan.sw.n_blocks > 0)
         return false;
     return m->opts.ccsell == 1 || m->n_cols >= ((int64_t)1 << 23);
@@ -853,14 +833,12 @@ sm_status upload_sell_layouts(sm_matrix *m, const int32_t *rp, const int32_t *co
         rpc[(size_t)r + 1] = (int32_t)oc;
     }
     std::vector<int32_t>().swap(rcol);
-    sm_status st = build_band2(m, p.hot, nr, H0, hot, rph.data(), ch.data(), vh.data(), kXbCband,
-                               0, 0, true);
-    if (st != SM_OK) return st;
+    const size_t mark = m->mem.mark();
+    if (const sm_status st = build_band2(m, p.hot, nr, H0, hot, rph.data(), ch.data(), vh.data(), kXbCband, 0, 0, true))
+        return st;
     if (p.hot.n_blocks == 0 || p.hot.kind != kXbCband) {   // not applicable: sell serves all terms
-        XbandDev &h = p.hot;   // released and uncounted: the matrix is as if it was never tried
-        m->mem.release(h.d_chunk_start, h.d_word, h.d_val, h.d_partials, h.d_tickets, h.d_band_clo, h.d_table,
-                       h.d_pace, h.d_term);
-        h = XbandDev();
+        m->mem.release_since(mark);   // the matrix is as if the split was never tried
+        p.hot = Band2Dev();
         return upload_sell(m, rp, col, val);
     }
     p.hot_cols = (int32_t)H0;
@@ -1001,11 +979,15 @@ sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell) {
         int32_t slabs = 1;
         gcb_geometry(m, rows_log2, slabs);
         GcbHost meta;
+        const size_t mark = m->mem.mark();
         const int rc = devbuild_gcb(m, rows_log2, slabs, kGcbMaxWindow, meta, s, eb);
         if (rc < 0) st = hip_fail(eb, "device gcb builder");
         else if (rc == 0) {
             st = gcb_finish(m, meta);
             dev_done = st == SM_OK;
+        } else {   // declined: nothing of the attempt stays
+            m->mem.release_since(mark);
+            m->plan.gcb = GcbDev();
         }
     }
     if (dev_ok && !xband) {

@@ -89,35 +89,51 @@ struct alignas(16) Chunk {
     int32_t lr, begin, end, pad;
 };
 
-// Device copy of the column-band layout (xband.h).
-struct XbandDev {
-    int32_t kind = 0;                 // XbKind; 0 when not built
-    int32_t threads = 0;              // workgroup size of the kind
-    int32_t block_rows = 0, band_cols = 0, n_blocks = 0, n_bands = 0;
-    int32_t n_slabs = 1, slab_bands = 0;   // tiles = n_blocks * n_slabs
-    int32_t slab0_cols = 0;           // band2 / cband: columns of slab 0 (others: slab_bands)
-    int64_t n_chunks = 0;
-    int64_t max_chunks_per_band = 0;
-    int32_t *d_chunk_start = nullptr;
-    uint32_t *d_word = nullptr;
-    float *d_val = nullptr;
-    float *d_partials = nullptr;      // (n_slabs - 1) * n_rows slab partial sums (one SpMV in flight)
+// Device copies of the column-band layouts (xband.h, gcb.h): three families of different bytes.
+// BandTiles is what all of them hold under one meaning: tiles = n_blocks * n_slabs, each tile a
+// block of rows times a slab of columns, walked band by band.
+struct BandTiles {
+    int32_t kind = 0;                 // XbKind (sm_info.has_xband); 0 when not built
+    int32_t block_rows = 0, n_blocks = 0, n_bands = 0;   // n_blocks == 0 when not built
+    int32_t n_slabs = 1;
+    // Slab scratch (alloc_slab_scratch; null with one slab), one SpMV in flight:
+    float *d_partials = nullptr;      // row sets of slab partial sums
     int32_t *d_tickets = nullptr;     // 4 x n_blocks slab hand-off control words, zero between SpMVs
-    // band2 kind (band2.cpp): d_chunk_start = tile -> first band (n_tiles + 1), d_word =
-    // the lane-interleaved entries (4096 per band), d_band_clo = each band's first column.
-    int32_t *d_band_clo = nullptr;
-    // cband kind: the codebook (table_size <= 255 floats) the entries' ids index.
-    float *d_table = nullptr;
-    int32_t table_size = 0;
-    // gcb kind: column pacing words (kernels_gcb.hip), 8 x (1 + pace_k) monotonic counters.
-    int32_t *d_pace = nullptr;
-    int32_t pace_k = 0;
     // Updatable matrices (sm_build_opts.updatable): the slot -> term map of the kinds that hold
-    // their own copy of the values.  exact / blocked / gather: one entry per d_val slot
-    // (n_term = the slots); band2 / gcb: two per 16-byte lane entry of d_word (n_term = the
-    // entries).  -1: a dummy slot.
+    // their own copy of the values, -1: a dummy slot.  XbandDev: one entry per d_val slot (n_term =
+    // the slots); Band2Dev / GcbDev: two per 16-byte lane entry of d_ent (n_term = the entries).
     int32_t *d_term = nullptr;
     int64_t n_term = 0;
+};
+
+// Exact / blocked / gather kinds (xband.cpp, kernels_xband.hip).
+struct XbandDev : BandTiles {
+    int32_t *d_chunk_start = nullptr; // per (block, band): its first chunk
+    uint32_t *d_word = nullptr;       // per slot: row, rank and column in the band
+    float *d_val = nullptr;           // per slot
+    int32_t slab_bands = 0, band_cols = 0;   // bands per slab (a multiple of 8), columns per band
+    int64_t max_chunks_per_band = 0;  // register capacity the launcher picks its kernel by
+    int32_t slab_cols() const { return (int32_t)std::min<int64_t>((int64_t)slab_bands * band_cols, INT32_MAX); }
+};
+
+// Band2 / cband kinds (band2.cpp, kernels_band2.hip); also the hot column prefix (Plan::hot).
+struct Band2Dev : BandTiles {
+    int32_t *d_tile_band = nullptr, *d_band_clo = nullptr;   // tile -> first band (tiles + 1), each band's first column
+    uint32_t *d_ent = nullptr;        // lane-interleaved entries: band2 column/row + value, cband words
+    float *d_table = nullptr;         // cband: the codebook (table_size <= 255 of 256 floats) the ids index
+    int32_t table_size = 0;
+    int32_t window = 0;               // x columns a band stages (B2Geom::window)
+    int32_t slab_cols = 0, slab0_cols = 0;   // columns per slab s >= 1, and of slab 0
+};
+
+// Gathered chunk bands (gcb.cpp / builddev_gcb.hip, kernels_gcb.hip).
+struct GcbDev : BandTiles {
+    int32_t *d_tile_band = nullptr, *d_band_clo = nullptr;   // tile -> first band (tiles + 1), each band's first column
+    uint32_t *d_ent = nullptr;        // lane-interleaved entries, kGcbBandWords per band
+    int32_t slab_cols = 0, window = 0;   // columns per slab, the widest column range of a band
+    // Column pacing words (kernels_gcb.hip), 8 x (1 + pace_k) monotonic counters.
+    int32_t *d_pace = nullptr;
+    int32_t pace_k = 0;
 };
 
 // Device copy of the sorted sliced-ELL layout (sell.h).
@@ -225,8 +241,21 @@ hipError_t launch_spmv_merge(int32_t n, int32_t nnz, const int32_t *rp, const in
                              hipStream_t s, const MergeStage *stage = nullptr);
 
 struct Plan {
-    XbandDev xb;                      // n_blocks == 0 when not built
-    SellDev sell;                     // n_slices == 0 when not built
+    // The band layout: at most one of the three families is built (n_blocks == 0 when not).
+    XbandDev xb;
+    Band2Dev b2;
+    GcbDev gcb;
+    // What the built family shares with the others (built at all? how many slabs?), or null.
+    const BandTiles *band() const {
+        if (xb.n_blocks > 0) return &xb;
+        if (b2.n_blocks > 0) return &b2;
+        return gcb.n_blocks > 0 ? &gcb : nullptr;
+    }
+    int32_t band_slabs() const { return band() ? band()->n_slabs : 0; }
+    // Columns per slab, and of slab 0 (band2 / cband may make it narrower); 0 without bands.
+    int32_t band_slab_cols() const { return xb.n_blocks > 0 ? xb.slab_cols() : b2.n_blocks > 0 ? b2.slab_cols : gcb.slab_cols; }
+    int32_t band_slab0_cols() const { return b2.n_blocks > 0 && b2.slab0_cols > 0 ? b2.slab0_cols : band_slab_cols(); }
+    SellDev sell;                    // n_slices == 0 when not built
     // Unsegmented sorted sliced ELL (every row, any length, in the reference's order):
     // SM_ALGO_EXACT's kernel when no other built layout keeps that order.
     SellDev xsell;
@@ -235,7 +264,7 @@ struct Plan {
     SweepDev sw;                      // n_blocks == 0 when not built
     // Skewed graphs: the hottest relabeled columns [0, hot_cols) as codebook bands (x in
     // LDS), the sell layout holding only the other terms.
-    XbandDev hot;                     // n_blocks == 0 when not built
+    Band2Dev hot;                     // n_blocks == 0 when not built
     int32_t hot_cols = 0;
     int32_t tile_nnz = kTileNnz;      // one of 1024, 2048, 4096, 8192
     int32_t n_tiles = 0;
@@ -285,13 +314,17 @@ hipError_t launch_spmv_ccsell(const CcsellDev &cd, const float *x, float *y, flo
 // AddMatMat on the reference's stream (native.hip): C = alpha * A * S + beta * C.
 hipError_t launch_native_addmatmat(const NativeDev &nd, int32_t m, const float *a, int32_t lda,
                                    float *c, int32_t ldc, float alpha, float beta, hipStream_t s);
-// Balanced-band kind (kernels_band2.hip).
-// Gathered chunk bands (gcb.h, kernels_gcb.hip): d_chunk_start = tile -> first band,
-// d_band_clo, d_word = the lane-interleaved entries (kGcbBandWords per band).
-hipError_t launch_spmv_gcb(const XbandDev &xb, int32_t n_rows, int32_t n_cols, const float *x, float *y,
+// Gathered chunk bands (kernels_gcb.hip) and the balanced-band kinds (kernels_band2.hip).
+hipError_t launch_spmv_gcb(const GcbDev &xb, int32_t n_rows, int32_t n_cols, const float *x, float *y,
                            float alpha, float beta, hipStream_t s);
-hipError_t launch_spmv_band2(const XbandDev &xb, int32_t n_rows, int32_t n_cols, const float *x,
+hipError_t launch_spmv_band2(const Band2Dev &xb, int32_t n_rows, int32_t n_cols, const float *x,
                              float *y, float alpha, float beta, hipStream_t s);
+// The launcher of the band family the plan has built (Plan::band() is not null).
+inline hipError_t launch_spmv_band(const Plan &p, int32_t n, int32_t nc, const float *x, float *y, float a, float b, hipStream_t s) {
+    if (p.b2.n_blocks > 0) return launch_spmv_band2(p.b2, n, nc, x, y, a, b, s);
+    if (p.gcb.n_blocks > 0) return launch_spmv_gcb(p.gcb, n, nc, x, y, a, b, s);
+    return launch_spmv_xband(p.xb, n, nc, x, y, a, b, s);
+}
 // xp[rank[c]] = x[c], c < n (rank: original column -> new column).
 hipError_t launch_x_relabel(int64_t n, const int32_t *rank, const float *x, float *xp,
                             hipStream_t s);
@@ -387,9 +420,10 @@ sm_status upload_native(sm_matrix *m);
 // for the unsegmented sliced ELL built for it.
 constexpr int kAlgoExactSell = 100;
 int exact_algo(const sm_matrix *m, bool x16);
-// The gathered chunk bands (builddev_gcb.hip): gcb_build's bytes into m->plan.xb's d_chunk_start,
-// d_band_clo and d_word, the geometry in `meta` (its vectors stay empty).  0 built, 1 declined as
-// gcb_build would, < 0 on a HIP error (err) or a builder inconsistency.
+// The gathered chunk bands (builddev_gcb.hip): gcb_build's bytes into m->plan.gcb's d_tile_band,
+// d_band_clo and d_ent, the geometry in `meta` (its vectors stay empty).  0 built, 1 declined as
+// gcb_build would (the caller drops what it allocated till then: DevMem::release_since), < 0 on
+// a HIP error (err) or a builder inconsistency.
 struct GcbHost;
 int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, GcbHost &meta, hipStream_t s,
                  hipError_t &err);

@@ -235,6 +235,27 @@ def test_devbuild_gcb_ragged_and_declines(sm):
     assert info2["has_xband"] != 6, info2
 
 
+def test_devbuild_gcb_declined_leaves_nothing(sm):
+    """A forced gcb layout on a small matrix with one row whose columns are not ascending: the
+    device builder declines, the host path decides (gcb.cpp declines too), and nothing of the
+    attempt stays -- every info field (device_bytes among them) and the digest equal the host
+    build's."""
+    from gpu_util import uniform_csr
+    torch = torch_dev()
+    n_rows, n_cols = 2048, 16384
+    rp, ci, va = uniform_csr(n_rows, n_cols, 8, seed=31)
+    ci = ci.copy()
+    a = int(rp[1000])
+    assert ci[a] < ci[a + 1]
+    ci[a], ci[a + 1] = ci[a + 1], ci[a]
+    dev = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in (rp, ci, va)]
+    D, H = (sm.SparseMatrix.from_csr(*dev, n_cols, opts=dict(layout="gcb", host_build=hb)) for hb in (0, 1))
+    di, hi = D.info(), H.info()
+    assert di == hi, (di, hi)
+    assert di["has_xband"] != 6, di
+    assert D.layout_digest() == H.layout_digest()
+
+
 def test_devbuild_gcb_config5_rank0_slice(sm):
     """Config 5's rank-0 slice as bench.py builds it (2^23 rows x 2^26 columns, 16 per row,
     seed 5), AUTO: the device build byte-identical to the host's, under 1.5 s, the SpMV the

@@ -206,6 +206,32 @@ def test_hot_bands_forced_skewed(sm, hot):
         _check(M, rp, ci, va, x, y0, alpha, beta, exact_max=0)
 
 
+def test_declined_hot_split_leaves_nothing(sm):
+    """A hot split that is tried and refused: 32768 independent values (far more than 255 bit
+    patterns), so the hot prefix builds as 8-byte band2 entries, which the split does not take.
+    The matrix is then the one built without hot_cols -- every info field (hot_cols == 0 and
+    device_bytes among them) and the layout digest -- and its rows, all short, keep the
+    reference's order."""
+    rng = np.random.default_rng(21)
+    n_rows, n_cols, per = 4096, 16384, 8
+    ci = np.sort(np.stack([rng.choice(n_cols, per, replace=False) for _ in range(n_rows)]), axis=1)
+    ci = ci.reshape(-1).astype(np.int32)
+    rp = np.arange(0, n_rows * per + 1, per, dtype=np.int32)
+    va = rng.uniform(-1, 1, n_rows * per).astype(np.float32)
+    assert np.unique(va.view(np.uint32)).size > 255
+    T = sm.SparseMatrix.from_csr(rp, ci, va, n_cols, opts=dict(layout="no_bands", relabel=1, hot_cols=2048))
+    P = sm.SparseMatrix.from_csr(rp, ci, va, n_cols, opts=dict(layout="no_bands", relabel=1))
+    ti, pi = T.info(), P.info()
+    assert ti == pi, (ti, pi)
+    assert ti["hot_cols"] == 0 and ti["sell_slices"] > 0 and ti["col_relabel"] == 1, ti
+    assert T.layout_digest() == P.layout_digest()
+    x = rng.uniform(-1, 1, n_cols).astype(np.float32)
+    y0 = rng.uniform(-1, 1, n_rows).astype(np.float32)
+    y = to_dev(y0)
+    T.spmv(to_dev(x), y, 1.3, 0.7)
+    assert np.array_equal(bits(to_host(y)), bits(oracle.csr_spmv(rp, ci, va, x, y0, 1.3, 0.7)))
+
+
 def test_config4_rmat24_auto_vs_oracle(sm):
     """BASELINE config 4 at full size, exactly as bench.py builds it: Graph500 R-MAT
     scale 24, edgefactor 16, seed 4 (263 M terms, rows up to 238 465 terms), AUTO =
