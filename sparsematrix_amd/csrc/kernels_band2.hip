@@ -143,6 +143,8 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
     // Band windows: lane l holds clo of bands cw + l (lo) and cw + 64 + l (hi), read by
     // readlane; the window advances by 64 bands when the x loads reach its hi half.
     const int32_t *clg = band_clo + g0;
+    // xband_dev.h LaneWindow<false>, kept inline: with the struct hipcc allocates the wide
+    // kernels' registers differently.
     int32_t cw = 0;
     int32_t clo_lo = lane < nb ? clg[lane] : 0;
     int32_t clo_hi = 64 + lane < nb ? clg[64 + lane] : 0;
@@ -185,14 +187,7 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
 #pragma unroll
         for (int m = 0; m < W / 256; ++m) {
             const uint32_t voff = 4u * (uint32_t)(c + m * 256 + lane * 4);
-            const uint32_t lds = __builtin_amdgcn_readfirstlane(xs_lds + 4u * (uint32_t)(buf * W + m * 256));
-            uint32_t keep;
-            asm volatile(
-                "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "v"(voff), "s"(x_src), "s"(lds)
-                : "memory");
+            lds_dma_1k(voff, x_src, __builtin_amdgcn_readfirstlane(xs_lds + 4u * (uint32_t)(buf * W + m * 256)));
         }
     };
     // Entries of band q: band2 {word 2w, word 2w+1, value 2w, value 2w+1}, cband {word 2w,
@@ -208,12 +203,6 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
             return __builtin_amdgcn_raw_buffer_load_b128(e_src, off, 0, kAuxNt);
     };
 
-    auto shr1 = [](float v) {   // lane i <- lane i-1 (lane 0 never has rank >= 1)
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xF, 0xF, false));
-    };
-    auto shl1 = [](uint32_t v) {   // lane i <- lane i+1; lane 63 <- the dummy rank
-        return (uint32_t)__builtin_amdgcn_update_dpp((int)kB2DummyRank, (int)v, 0x130, 0xF, 0xF, false);
-    };
     // band2 apply in two steps (b2_read issues the four LDS reads, b2_finish adds and writes;
     // the wide loop stores the next x window between them).
     struct B2State {
@@ -252,12 +241,13 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
             tm[k] = __fmul_rn(xv[k], __fmul_rn(st.va[k], alpha));
             acc[k] = __fadd_rn(yv[k], tm[k]);
         }
+        // Rank rounds, inline in every kernel: as a shared function hipcc compiles the loop differently.
         if (__any(st.more)) {
             for (uint32_t r = 1;; ++r) {
                 bool again = false;
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    const float prev = shr1(acc[k]);
+                    const float prev = dpp_shr1(acc[k]);
                     if (rk[k] == r) acc[k] = __fadd_rn(prev, tm[k]);
                     again |= live[k] && rk[k] > r;
                 }
@@ -266,7 +256,7 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {   // the segment's last lane writes its row
-            const bool last = live[k] && shl1(rk[k]) != rk[k] + 1u;
+            const bool last = live[k] && dpp_shl1(rk[k], kB2DummyRank) != rk[k] + 1u;
             if constexpr (kScratch)
                 yacc[last ? rl[k] : (uint32_t)(BROWS + lane)] = acc[k];   // every lane writes
             else if (last)
@@ -275,8 +265,8 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
         __builtin_amdgcn_s_setprio(0);
     };
 
-    // Lane select by an SGPR lane mask (v_cndmask_b32 with the mask as its condition):
-    // lane i takes b where bit i of m is set, else a.
+    // xband_dev.h lane_select and, below, mask_rounds, kept inline: with the header functions
+    // hipcc allocates the wide cband kernel's registers differently.
     auto sel = [](uint64_t m, float a, float bb) -> float {
         float r;
         asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(bb), "s"(m));
@@ -327,7 +317,7 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
         while ((R[0] | R[1]) != 0) {
 #pragma unroll
             for (int k = 0; k < CPW; ++k) {
-                acc[k] = sel(R[k], acc[k], __fadd_rn(shr1(acc[k]), tm[k]));
+                acc[k] = sel(R[k], acc[k], __fadd_rn(dpp_shr1(acc[k]), tm[k]));
                 R[k] = st.cont[k] & (R[k] << 1);
             }
         }
@@ -383,6 +373,7 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
     // Accumulators: beta*y (slab 0 of a one-slab layout, or of any layout without SM_B2_BL) or
     // -0.0 (the identity of fp32 addition: a row without terms in this slab keeps the sign of a
     // zero y), all loads in flight.
+    // (Inline in every band kernel: moved into a shared function, hipcc allocates and schedules differently.)
     constexpr int kQ = BROWS / (4 * kB2Threads);
     const bool y_vec = ((uintptr_t)(y + r0) & 15) == 0;
     const bool y_first = slab == 0 && (n_slabs == 1 || !SM_B2_BL);
@@ -529,13 +520,7 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
 #endif
     };
     if (n_slabs == 1) {
-        const int32_t nv = y_vec ? (nr & ~3) : 0;   // float4 rows, then the rest
-#pragma unroll
-        for (int q = 0; q < kQ; ++q) {
-            const int32_t i = 4 * (tid + q * kB2Threads);
-            if (i < nv) *reinterpret_cast<float4 *>(y + r0 + i) = *reinterpret_cast<const float4 *>(&yacc[i]);
-        }
-        for (int32_t i = nv + tid; i < nr; i += kB2Threads) y[r0 + i] = yacc[i];
+        tile_store_y<kB2Threads, BROWS>(yacc, y, r0, nr, y_vec);
         flush_prof();
         return;
     }
@@ -553,22 +538,29 @@ __global__ __launch_bounds__(kB2Threads) void spmv_band2_kernel(
     flush_prof();
 }
 
+// One launch over a Band2Dev: a workgroup per (row block, slab).
+template <bool CB, int GEO, int PROF = 0>
+hipError_t launch_b2_tiles(const Band2Dev &xb, int32_t n_rows, int32_t n_cols, const float *x, float *y,
+                           float alpha, float beta, hipStream_t s) {
+    hipLaunchKernelGGL((spmv_band2_kernel<CB, GEO, PROF>), dim3((unsigned)((int64_t)xb.n_blocks * xb.n_slabs)),
+                       dim3(kB2Threads), 0, s, n_rows, n_cols, xb.block_rows, xb.n_slabs, xb.d_tile_band,
+                       xb.d_band_clo, xb.d_ent, xb.d_table, xb.table_size, x, y, xb.d_partials, xb.d_tickets,
+                       alpha, beta);
+    return hipGetLastError();
+}
+
 #ifdef SM_DEV
 // Development read-out of PROF 1 / 2 (tools/cband_prof.py).
 template <int GEO>
-hipError_t launch_prof(int prof, dim3 grid, hipStream_t s, const Band2Dev &xb, int32_t n_rows, int32_t n_cols,
+hipError_t launch_prof(int prof, hipStream_t s, const Band2Dev &xb, int32_t n_rows, int32_t n_cols,
                        const float *x, float *y, float alpha, float beta) {
-#define SM_B2P(P)                                                                                   \
-    hipLaunchKernelGGL((spmv_band2_kernel<true, GEO, P>), grid, dim3(kB2Threads), 0, s, n_rows, n_cols, \
-                       xb.block_rows, xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent,          \
-                       xb.d_table, xb.table_size, x, y, xb.d_partials, xb.d_tickets, alpha, beta)
     if (prof == 1) {
         if (GEO != 4) return hipErrorInvalidValue;
         unsigned long long h[8] = {};
         void *sym = nullptr;
         if (hipGetSymbolAddress(&sym, HIP_SYMBOL(g_b2_prof)) != hipSuccess) return hipErrorInvalidValue;
         (void)hipMemsetAsync(sym, 0, sizeof(h), s);
-        SM_B2P(1);
+        if (const hipError_t e = launch_b2_tiles<true, GEO, 1>(xb, n_rows, n_cols, x, y, alpha, beta, s)) return e;
         (void)hipMemcpyAsync(h, sym, sizeof(h), hipMemcpyDeviceToHost, s);
         (void)hipStreamSynchronize(s);
         const double wa = (double)(h[7] & 0xFFFFFFFFull), wl = (double)(h[7] >> 32);
@@ -579,13 +571,12 @@ hipError_t launch_prof(int prof, dim3 grid, hipStream_t s, const Band2Dev &xb, i
                 h[3] / wl / bands, h[4] / wl / bands, h[5] / wl / bands);
         return hipGetLastError();
     }
-    const int nt = (int)std::min<int64_t>(grid.x, 4096);
+    const int nt = (int)std::min<int64_t>((int64_t)xb.n_blocks * xb.n_slabs, 4096);
     std::vector<unsigned long long> h((size_t)kTs * nt);
     void *sym = nullptr;
     if (hipGetSymbolAddress(&sym, HIP_SYMBOL(g_b2_ts)) != hipSuccess) return hipErrorInvalidValue;
     (void)hipMemsetAsync(sym, 0, h.size() * 8, s);
-    SM_B2P(2);
-#undef SM_B2P
+    if (const hipError_t e = launch_b2_tiles<true, GEO, 2>(xb, n_rows, n_cols, x, y, alpha, beta, s)) return e;
     (void)hipMemcpyAsync(h.data(), sym, h.size() * 8, hipMemcpyDeviceToHost, s);
     (void)hipStreamSynchronize(s);
     unsigned long long t0 = ~0ull;
@@ -645,7 +636,6 @@ hipError_t launch_spmv_band2(const Band2Dev &xb, int32_t n_rows, int32_t n_cols,
         (cb && (!xb.d_table || xb.table_size < 0 || xb.table_size > (int32_t)kCbDummyId)) ||
         (xb.n_slabs > 1 && (!xb.d_partials || !xb.d_tickets)))
         return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((int64_t)xb.n_blocks * xb.n_slabs));
 #ifdef SM_DEV
     static const int prof = [] {
         const char *e = dev_env("SM_BAND2_PROF");
@@ -653,21 +643,15 @@ hipError_t launch_spmv_band2(const Band2Dev &xb, int32_t n_rows, int32_t n_cols,
     }();
     if (prof != 0) {
         if (!cb) return hipErrorInvalidValue;
-        return dma3 ? launch_prof<4>(prof, grid, s, xb, n_rows, n_cols, x, y, alpha, beta)
-                    : launch_prof<0>(prof, grid, s, xb, n_rows, n_cols, x, y, alpha, beta);
+        return dma3 ? launch_prof<4>(prof, s, xb, n_rows, n_cols, x, y, alpha, beta)
+                    : launch_prof<0>(prof, s, xb, n_rows, n_cols, x, y, alpha, beta);
     }
 #endif
-#define SM_B2(C, T)                                                                                 \
-    hipLaunchKernelGGL((spmv_band2_kernel<C, T, 0>), grid, dim3(kB2Threads), 0, s, n_rows, n_cols,    \
-                       xb.block_rows, xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent,          \
-                       xb.d_table, xb.table_size, x, y, xb.d_partials, xb.d_tickets, alpha, beta)
-    if (dma3) {
-        if (cb) SM_B2(true, 4); else SM_B2(false, 4);
-    } else {
-        if (cb) SM_B2(true, 0); else SM_B2(false, 0);
-    }
-#undef SM_B2
-    return hipGetLastError();
+    if (dma3)
+        return cb ? launch_b2_tiles<true, 4>(xb, n_rows, n_cols, x, y, alpha, beta, s)
+                  : launch_b2_tiles<false, 4>(xb, n_rows, n_cols, x, y, alpha, beta, s);
+    return cb ? launch_b2_tiles<true, 0>(xb, n_rows, n_cols, x, y, alpha, beta, s)
+              : launch_b2_tiles<false, 0>(xb, n_rows, n_cols, x, y, alpha, beta, s);
 }
 
 }  // namespace smamd

@@ -31,15 +31,12 @@ constexpr int kGcbThreads = 1024;
 
 // ABL (development builds, SM_GCB_ABLATE; results wrong): 1 no x gathers (x read as 0,
 // no memory request), 2 no apply (the loaded values kept live), 4 no per-band barrier.
-// PACE: column pacing (below), a development A/B until measured.
-// XAUX: cache-policy bits of the x gathers (development A/B).
-template <int ROWS_LOG2, int ER, int GA, int ABL = 0, bool PACE = false, int XAUX = 0>
+template <int ROWS_LOG2, int ER, int GA, int ABL = 0>
 __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
     int32_t n_rows, int32_t n_cols, int32_t block_rows, int32_t n_slabs,
     const int32_t *__restrict__ tile_band_start, const int32_t *__restrict__ band_clo,
     const uint32_t *__restrict__ ent, const float *__restrict__ x, float *__restrict__ y,
-    float *__restrict__ partials, int32_t *__restrict__ ctl, float alpha, float beta,
-    int32_t *__restrict__ pace, int32_t pace_k, int32_t pace_slack) {
+    float *__restrict__ partials, int32_t *__restrict__ ctl, float alpha, float beta) {
     constexpr int BROWS = 1 << ROWS_LOG2;
     constexpr int XR = GA + 1;                  // x-value ring: band p's slot is not refilled at p
     constexpr int U = ER % XR == 0 ? ER : ER * XR;   // unroll: static ring roles
@@ -53,20 +50,6 @@ __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
     const int32_t b = t / n_slabs;
     const int32_t slab = t - b * n_slabs;
     handoff_started(ctl + (int64_t)b * kCtlWords, n_slabs);
-    // Column pacing (pace != null): the tiles of one dispatch group (blockIdx mod 8: one XCD
-    // under round-robin dealing, for speed only) sweep the columns together, so the x lines
-    // one tile gathers are still in the XCD's L2 when the group's other tiles reach them.  A
-    // tile adds 1 to checkpoint k's counter when its bands pass column k * 2^18, and before
-    // going past checkpoint k waits until every STARTED tile of its group has passed
-    // k - slack -- the slowest tile never waits, so the group always progresses.  Counters
-    // are monotonic across launches (launches on a matrix are ordered): this launch's counts
-    // are the values minus gen_base = launch index * group size.
-    const int32_t pg = (int32_t)(blockIdx.x & 7u);
-    const int32_t pn = ((int32_t)gridDim.x - pg + 7) / 8;   // tiles in the group
-    int32_t *pw = PACE ? pace + (int64_t)pg * (1 + pace_k) : nullptr;
-    int32_t gen_base = 0, kdone = -1;
-    if (PACE && tid == 0)
-        gen_base = __hip_atomic_fetch_add(pw, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / pn * pn;
     const int32_t g0 = tile_band_start[t];
     const int32_t nb = tile_band_start[t + 1] - g0;
     const int32_t r0 = b * block_rows;
@@ -77,20 +60,7 @@ __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
     // Band windows: lane l holds clo of bands cw + l (lo) and cw + 64 + l (hi); the
     // window moves on when the band gathered next leaves its low half.
     const int32_t *clg = band_clo + g0;
-    int32_t cw = 0;
-    int32_t clo_lo = lane < nb ? clg[lane] : 0;
-    int32_t clo_hi = 64 + lane < nb ? clg[64 + lane] : 0;
-    auto clo_at = [&](int32_t q) -> int32_t {   // q in [cw, cw + 128), wave-uniform
-        const int32_t j = q - cw;
-        const int32_t lo = __builtin_amdgcn_readlane(clo_lo, j & 63);
-        const int32_t hi = __builtin_amdgcn_readlane(clo_hi, j & 63);
-        return j < 64 ? lo : hi;
-    };
-    auto advance = [&]() {
-        cw += 64;
-        clo_lo = clo_hi;
-        clo_hi = cw + 64 + lane < nb ? clg[cw + 64 + lane] : 0;
-    };
+    LaneWindow<false> clo(clg, nb, lane);
     // Entries of band q for this lane: {word 2w, word 2w+1, value 2w, value 2w+1};
     // past the tile: zeros = dummies (no memory request).
     auto load_e = [&](int32_t q) -> u32x4 {
@@ -100,22 +70,14 @@ __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
     };
     // x of band q's two terms; dummies and headers read nothing (offset past the range).
     auto gather = [&](int32_t q, u32x4 e, float *xv) {
-        const int32_t c = q < nb ? clo_at(q) : 0;
+        const int32_t c = q < nb ? clo.at(q) : 0;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const uint32_t w = e[k];
             const uint32_t off = ((w & kGcbLive) && !(ABL & 1)) ? 4u * (uint32_t)(c + (int32_t)(w & kGcbColMask))
                                                                 : 0xFFFFFFF0u;
-            xv[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_src, off, 0, XAUX));
+            xv[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_src, off, 0, 0));
         }
-    };
-    auto shr1 = [](float v) {   // lane i <- lane i-1
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xF, 0xF, false));
-    };
-    auto sel = [](uint64_t m, float a, float bb) -> float {   // lane i: bb where bit i of m, else a
-        float r;
-        asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(bb), "s"(m));
-        return r;
     };
     auto apply = [&](u32x4 e, const float *xv) {
         __builtin_amdgcn_s_setprio(2);
@@ -138,13 +100,7 @@ __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
             acc[k] = __fadd_rn(yv[k], tm[k]);
             R[k] = cont[k] & ~(cont[k] << 1);
         }
-        while ((R[0] | R[1]) != 0) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                acc[k] = sel(R[k], acc[k], __fadd_rn(shr1(acc[k]), tm[k]));
-                R[k] = cont[k] & (R[k] << 1);
-            }
-        }
+        mask_rounds<2>(acc, tm, cont, R);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {   // the segment's last lane writes its row
             const uint64_t last = live[k] & ~(cont[k] >> 1);
@@ -161,6 +117,7 @@ __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
     for (int v = 0; v < ER; ++v) E[v] = load_e(v);
 #pragma unroll
     for (int v = 0; v < GA; ++v) gather(v, E[v], XV[v]);
+    // (Inline in every band kernel: moved into a shared function, hipcc allocates and schedules differently.)
     constexpr int kQ = BROWS / (4 * kGcbThreads);
     const bool y_vec = ((uintptr_t)(y + r0) & 15) == 0;
     if (slab == 0) {
@@ -201,22 +158,7 @@ __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int32_t q = p + u;
-            if (q + GA >= cw + 64) advance();   // the gather below reads clo of band q + GA
-            if (PACE && tid == 0 && q + GA < nb) {   // checkpoints passed by the band gathered next
-                const int32_t kq = min(clo_at(q + GA) >> kGcbColBits, pace_k - 1);
-                for (int32_t k = kdone + 1; k <= kq; ++k)
-                    __hip_atomic_fetch_add(pw + 1 + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (kq > kdone && kq >= pace_slack) {
-                    const int32_t kw = kq - pace_slack;
-                    for (;;) {
-                        const int32_t st = min(pn, __hip_atomic_load(pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - gen_base);
-                        const int32_t ar = __hip_atomic_load(pw + 1 + kw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - gen_base;
-                        if (ar >= st) break;
-                        __builtin_amdgcn_s_sleep(8);
-                    }
-                }
-                kdone = max(kdone, kq);
-            }
+            if (q + GA >= clo.cw + 64) clo.advance();   // the gather below reads clo of band q + GA
             gather(q + GA, E[(u + GA) % ER], XV[(u + GA) % XR]);
             if constexpr (ABL & 2) {
                 asm volatile("" ::"v"(E[u % ER].x), "v"(E[u % ER].y), "v"(E[u % ER].z), "v"(E[u % ER].w),
@@ -229,23 +171,30 @@ __global__ __launch_bounds__(kGcbThreads) void spmv_gcb_kernel(
         }
     }
 
-    if (PACE && tid < 64) {   // every checkpoint not yet passed, so the counts stay per launch
-        const int32_t kd = __builtin_amdgcn_readfirstlane(kdone);
-        for (int32_t k = kd + 1 + tid; k < pace_k; k += 64)
-            __hip_atomic_fetch_add(pw + 1 + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
     if (n_slabs == 1) {
-        const int32_t nv = y_vec ? (nr & ~3) : 0;   // float4 rows, then the rest
-#pragma unroll
-        for (int q = 0; q < kQ; ++q) {
-            const int32_t i = 4 * (tid + q * kGcbThreads);
-            if (i < nv) *reinterpret_cast<float4 *>(y + r0 + i) = *reinterpret_cast<const float4 *>(&yacc[i]);
-        }
-        for (int32_t i = nv + tid; i < nr; i += kGcbThreads) y[r0 + i] = yacc[i];
+        tile_store_y<kGcbThreads, BROWS>(yacc, y, r0, nr, y_vec);
         return;
     }
     slab_handoff<kGcbThreads>(yacc, ctl + (int64_t)b * kCtlWords, s_word, y, partials, n_rows, r0, nr,
                               slab, n_slabs, y_vec);
+}
+
+// Entries six bands ahead, x gathers two: 4/2, 6/3 and 8/4 measured 838 / 842 / 843 vs
+// 833 us on config 5's slice ("Round 4").
+constexpr int kGcbER = 6, kGcbGA = 2;
+
+template <int ABL>
+hipError_t launch_gcb_tiles(const GcbDev &xb, int32_t n_rows, int32_t n_cols, const float *x, float *y,
+                            float alpha, float beta, hipStream_t s) {
+    const dim3 grid((unsigned)((int64_t)xb.n_blocks * xb.n_slabs));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kGcbThreads), 0, s, n_rows, n_cols, xb.block_rows, xb.n_slabs,
+                           xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials, xb.d_tickets, alpha,
+                           beta);
+        return hipGetLastError();
+    };
+    return xb.block_rows > (1 << 14) ? launch(spmv_gcb_kernel<15, kGcbER, kGcbGA, ABL>)
+                                     : launch(spmv_gcb_kernel<14, kGcbER, kGcbGA, ABL>);
 }
 
 }  // namespace
@@ -257,80 +206,13 @@ hipError_t launch_spmv_gcb(const GcbDev &xb, int32_t n_rows, int32_t n_cols, con
         (xb.n_bands > 0 && !xb.d_ent) || (xb.n_slabs > 1 && (!xb.d_partials || !xb.d_tickets)) ||
         xb.block_rows > (1 << 15))
         return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((int64_t)xb.n_blocks * xb.n_slabs)), block(kGcbThreads);
-#define SM_GCB(RL, ER, GA)                                                                         \
-    hipLaunchKernelGGL((spmv_gcb_kernel<RL, ER, GA>), grid, block, 0, s, n_rows, n_cols, xb.block_rows, \
-                       xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,  \
-                       xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack)
-    int look = 0;
-    int32_t *pace = nullptr;
-    int32_t pace_slack = 0;
-    const bool tall = xb.block_rows > (1 << 14);
 #ifdef SM_DEV
-    if (const char *e = dev_env("SM_GCB_LOOK")) look = atoi(e);   // development A/B of ER/GA
-    if (const char *e = dev_env("SM_GCB_XAUX")) {   // x gather cache policy (A/B)
-        const int a = atoi(e);
-#define SM_GCBX(A)                                                                                 \
-    if (tall) hipLaunchKernelGGL((spmv_gcb_kernel<15, 6, 2, 0, false, A>), grid, block, 0, s, n_rows, n_cols,    \
-                                 xb.block_rows, xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y,  \
-                                 xb.d_partials, xb.d_tickets, alpha, beta, nullptr, 0, 0);                   \
-    else hipLaunchKernelGGL((spmv_gcb_kernel<14, 6, 2, 0, false, A>), grid, block, 0, s, n_rows, n_cols,         \
-                            xb.block_rows, xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y,       \
-                            xb.d_partials, xb.d_tickets, alpha, beta, nullptr, 0, 0)
-        switch (a) {
-        case 1: SM_GCBX(1); break;
-        case 2: SM_GCBX(2); break;
-        case 16: SM_GCBX(16); break;
-        case 17: SM_GCBX(17); break;
-        default: SM_GCBX(0); break;
-        }
-#undef SM_GCBX
-        return hipGetLastError();
-    }
-    if (const char *e = dev_env("SM_GCB_PACE")) {   // column pacing, slack in checkpoints (A/B)
-        pace_slack = atoi(e);
-        if (pace_slack > 0 && xb.d_pace) pace = xb.d_pace;
-    }
-    if (const char *e = dev_env("SM_GCB_ABLATE")) {
-        const int abl = atoi(e);
-#define SM_GCBA(A)                                                                                    \
-    if (tall) hipLaunchKernelGGL((spmv_gcb_kernel<15, 6, 2, A>), grid, block, 0, s, n_rows, n_cols, xb.block_rows, \
-                                 xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,  \
-                                 xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack);            \
-    else hipLaunchKernelGGL((spmv_gcb_kernel<14, 6, 2, A>), grid, block, 0, s, n_rows, n_cols, xb.block_rows, \
-                            xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,  \
-                            xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack)
-        switch (abl) {
-        case 1: SM_GCBA(1); break;
-        case 2: SM_GCBA(2); break;
-        case 3: SM_GCBA(3); break;
-        case 4: SM_GCBA(4); break;
-        case 5: SM_GCBA(5); break;
-        default: return hipErrorInvalidValue;
-        }
-#undef SM_GCBA
-        return hipGetLastError();
-    }
+    if (const char *e = dev_env("SM_GCB_ABLATE"))
+        return pick_int(atoi(e), std::integer_sequence<int, 1, 2, 3, 4, 5>{}, [&](auto abl) {
+            return launch_gcb_tiles<decltype(abl)::value>(xb, n_rows, n_cols, x, y, alpha, beta, s);
+        });
 #endif
-    if (pace) {
-        if (tall)
-            hipLaunchKernelGGL((spmv_gcb_kernel<15, 6, 2, 0, true>), grid, block, 0, s, n_rows, n_cols, xb.block_rows,
-                               xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,
-                               xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack);
-        else
-            hipLaunchKernelGGL((spmv_gcb_kernel<14, 6, 2, 0, true>), grid, block, 0, s, n_rows, n_cols, xb.block_rows,
-                               xb.n_slabs, xb.d_tile_band, xb.d_band_clo, xb.d_ent, x, y, xb.d_partials,
-                               xb.d_tickets, alpha, beta, pace, xb.pace_k, pace_slack);
-        return hipGetLastError();
-    }
-    switch (look) {
-    case 42: if (tall) SM_GCB(15, 4, 2); else SM_GCB(14, 4, 2); break;
-    case 63: if (tall) SM_GCB(15, 6, 3); else SM_GCB(14, 6, 3); break;
-    case 84: if (tall) SM_GCB(15, 8, 4); else SM_GCB(14, 8, 4); break;
-    default: if (tall) SM_GCB(15, 6, 2); else SM_GCB(14, 6, 2); break;
-    }
-#undef SM_GCB
-    return hipGetLastError();
+    return launch_gcb_tiles<0>(xb, n_rows, n_cols, x, y, alpha, beta, s);
 }
 
 }  // namespace smamd

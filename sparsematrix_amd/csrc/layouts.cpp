@@ -321,7 +321,7 @@ static void gcb_geometry(const sm_matrix *m, int &rows_log2, int32_t &slabs) {
 }
 
 // The rest of a built gcb layout (its bands already in d_tile_band / d_band_clo / d_ent):
-// the geometry, slab partials, hand-off and pacing words.
+// the geometry, slab partials and hand-off words.
 static sm_status gcb_finish(sm_matrix *m, const GcbHost &gh) {
     GcbDev &d = m->plan.gcb;
     d.kind = kXbGcb;
@@ -331,13 +331,7 @@ static sm_status gcb_finish(sm_matrix *m, const GcbHost &gh) {
     d.n_slabs = gh.n_slabs;
     d.window = gh.window;
     d.slab_cols = gh.slab_cols;
-    if (const sm_status sts = alloc_slab_scratch(m, d, m->n_rows, gh.n_slabs - 1)) return sts;
-    // Column pacing (kernels_gcb.hip): per dispatch group, a started count and one arrival
-    // count per 2^18-column checkpoint, monotonic across launches.
-    d.pace_k = (int32_t)((m->n_cols + kGcbMaxWindow - 1) / kGcbMaxWindow);
-    SM_TRY_HIP(m->mem.alloc(&d.d_pace, 8 * (1 + (int64_t)d.pace_k)));
-    SM_TRY_HIP(hipMemset(d.d_pace, 0, (size_t)8 * (1 + d.pace_k) * sizeof(int32_t)));
-    return SM_OK;
+    return alloc_slab_scratch(m, d, m->n_rows, gh.n_slabs - 1);
 }
 
 static sm_status upload_gcb(sm_matrix *m, const int32_t *rp, const int32_t *col, const float *val) {

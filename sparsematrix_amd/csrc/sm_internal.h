@@ -131,9 +131,6 @@ struct GcbDev : BandTiles {
     int32_t *d_tile_band = nullptr, *d_band_clo = nullptr;   // tile -> first band (tiles + 1), each band's first column
     uint32_t *d_ent = nullptr;        // lane-interleaved entries, kGcbBandWords per band
     int32_t slab_cols = 0, window = 0;   // columns per slab, the widest column range of a band
-    // Column pacing words (kernels_gcb.hip), 8 x (1 + pace_k) monotonic counters.
-    int32_t *d_pace = nullptr;
-    int32_t pace_k = 0;
 };
 
 // Device copy of the sorted sliced-ELL layout (sell.h).

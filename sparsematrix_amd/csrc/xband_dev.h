@@ -1,16 +1,28 @@
 // xband_dev.h -- device helpers shared by the band kernels (kernels_xband.hip,
-// kernels_band2.hip): range-checked buffer descriptors, vmcnt waits and the slab
-// hand-off of a row block's partial sums.
+// kernels_band2.hip, kernels_gcb.hip): range-checked buffer descriptors, vmcnt waits, the
+// tile helpers (lane shifts and selects, LDS-DMA, the lane-held table window, mask rounds,
+// the y store) and the slab hand-off of a row block's partial sums.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <utility>
 
 namespace smamd {
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// Host: f(std::integral_constant<int, A>) for the A of the list that equals v -- how the
+// launchers turn a run-time capacity or ablation number into a template argument.  A value
+// not in the list is an error.
+template <int... A, class F>
+hipError_t pick_int(int v, std::integer_sequence<int, A...>, F &&f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == A && (e = f(std::integral_constant<int, A>{}), true)) || ...);
+    return e;
+}
 
 // Range-checked buffer descriptor (wave-uniform): loads past `bytes` read 0, so
 // the prefetches below need no bounds branches (a branch around a load makes
@@ -32,6 +44,103 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// ---------------------------------------------------------------------------
+// Tile helpers: the pieces every band kernel is built from.
+
+// DPP wave shifts by one lane, how a row segment's running sum moves up consecutive lanes.
+__device__ __forceinline__ float dpp_shr1(float v) {   // lane i <- lane i-1; lane 0 <- 0 (it never continues a segment)
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xF, 0xF, false));
+}
+__device__ __forceinline__ uint32_t dpp_shl1(uint32_t v, uint32_t fill) {   // lane i <- lane i+1; lane 63 <- fill
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x130, 0xF, 0xF, false);
+}
+
+// Lane select by an SGPR lane mask (v_cndmask_b32 with the mask as its condition):
+// lane i takes b where bit i of m is set, else a.
+__device__ __forceinline__ float lane_select(uint64_t m, float a, float b) {
+    float r;
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(m));
+    return r;
+}
+
+// LDS-DMA of one 1 KiB piece (one wave-instruction, 16 bytes per lane): memory at `src` +
+// voff (per lane; past the descriptor's range: no request) to LDS address `lds`
+// (wave-uniform, the piece's first byte).  Issued from asm so hipcc does not count it (a
+// counted LDS-DMA makes hipcc drain vmcnt at every barrier and at every use of an ordinary
+// load); the caller retires it with wait_vmcnt before the barrier that publishes the piece.
+__device__ __forceinline__ void lds_dma_1k(uint32_t voff, __amdgpu_buffer_rsrc_t src, uint32_t lds) {
+    uint32_t keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(src), "s"(lds)
+        : "memory");
+}
+
+// A window of 128 entries over a per-band table of n entries, held in lanes: lane l holds
+// tab[cw + l] (lo) and tab[cw + 64 + l] (hi), read by readlane with a branch-free select.
+// Every 64 bands the window advances: hi (loaded 64 bands earlier) becomes lo and the next
+// hi is prefetched -- no load is waited for at once, and the prefetched half is not touched
+// (so not waited for) until it becomes lo.  Past the table: CLAMP repeats entry n (a table of
+// n + 1 boundaries), otherwise 0.
+template <bool CLAMP>
+struct LaneWindow {
+    const int32_t *tab;
+    int32_t n, lane, cw, lo, hi;
+    __device__ __forceinline__ int32_t fetch(int32_t i) const {
+        if constexpr (CLAMP) return tab[min(i, n)];
+        else return i < n ? tab[i] : 0;
+    }
+    __device__ __forceinline__ LaneWindow(const int32_t *t, int32_t n_, int32_t lane_)
+        : tab(t), n(n_), lane(lane_), cw(0), lo(fetch(lane_)), hi(fetch(64 + lane_)) {}
+    __device__ __forceinline__ void advance() {
+        cw += 64;
+        lo = hi;
+        hi = fetch(cw + 64 + lane);
+    }
+    __device__ __forceinline__ int32_t at(int32_t i) const {   // i in [cw, cw + 128), wave-uniform
+        const int32_t j = i - cw;
+        const int32_t l = __builtin_amdgcn_readlane(lo, j & 63);
+        const int32_t h = __builtin_amdgcn_readlane(hi, j & 63);
+        return j < 64 ? l : h;
+    }
+};
+
+// Rank rounds by SGPR lane mask: a segment's running sum moves up one lane per round in lane
+// (= column) order.  cont[k] marks the lanes that continue the row of the lane below; R[k]
+// holds the lanes of the first round, cont & ~(cont << 1), and each round updates the
+// continuations whose predecessor finished in the round before.
+template <int N>
+__device__ __forceinline__ void mask_rounds(float *acc, const float *t, const uint64_t *cont, uint64_t *R) {
+    auto pending = [&]() {
+        uint64_t m = R[0];
+#pragma unroll
+        for (int k = 1; k < N; ++k) m |= R[k];
+        return m;
+    };
+    while (pending() != 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            acc[k] = lane_select(R[k], acc[k], __fadd_rn(dpp_shr1(acc[k]), t[k]));
+            R[k] = cont[k] & (R[k] << 1);
+        }
+    }
+}
+
+// The tile's sums to y (one slab: no hand-off): float4 rows while y is aligned, then the rest.
+template <int THREADS, int BROWS>
+__device__ __forceinline__ void tile_store_y(const float *yacc, float *y, int32_t r0, int32_t nr, bool y_vec) {
+    const int32_t tid = threadIdx.x;
+    const int32_t nv = y_vec ? (nr & ~3) : 0;
+#pragma unroll
+    for (int q = 0; q < BROWS / (4 * THREADS); ++q) {
+        const int32_t i = 4 * (tid + q * THREADS);
+        if (i < nv) *reinterpret_cast<float4 *>(y + r0 + i) = *reinterpret_cast<const float4 *>(&yacc[i]);
+    }
+    for (int32_t i = nv + tid; i < nr; i += THREADS) y[r0 + i] = yacc[i];
 }
 
 // ---------------------------------------------------------------------------

@@ -6,6 +6,9 @@ Bit-exact targets: with one slab the reference's order (oracle.csr_spmv: every r
 terms in ascending column order, kernel.cc:780-796); with several, the slab-order
 restatement (gpu_util.slab_order_spmv) -- and always within 1e-6 * sum|terms| of the
 reference."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -132,3 +135,23 @@ def test_gcb_repeated_launches_reset_handoff(sm):
     want = slab_order_spmv(rp, ci, va, to_host(x), y0, 1.0, 0.5, info["xband_slab_cols"], info["xband_slab0_cols"])
     for y in ys:
         assert np.array_equal(bits(to_host(y)), bits(want))
+
+
+def test_gcb_info_equals_recorded_but_for_the_pacing_words(sm):
+    """tests/golden/gcb_info_691cd1d.json holds info() and the layout digest of the smallest gcb
+    matrix of SHAPES as the library of commit 691cd1d reported them on the MI355X.  That library gave
+    every gcb matrix column-pacing counters for a development experiment, 8 x (1 + ceil(n_cols /
+    2^18)) int32 device words; they are gone.  So device_bytes is lower by exactly their size and
+    nothing else in info() or the digest has moved."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gcb_info_691cd1d.json")) as f:
+        rec = json.load(f)
+    m = rec["matrix"]
+    assert (m["n_rows"], m["n_cols"], m["per_row"]) == SHAPES[4]
+    rp, ci, va = uniform_csr(m["n_rows"], m["n_cols"], m["per_row"], seed=m["seed"])
+    M, info = _gcb(sm, rp, ci, va, m["n_cols"], m["band_slabs"])
+    pacing_bytes = 4 * 8 * (1 + -(-m["n_cols"] // (1 << 18)))
+    assert pacing_bytes == 64
+    want = dict(rec["info"])
+    want["device_bytes"] -= pacing_bytes
+    assert info == want
+    assert [str(d) for d in M.layout_digest()] == rec["layout_digest"]
