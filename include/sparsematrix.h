@@ -22,6 +22,13 @@
  *     x * (v * alpha), added one at a time               kernel.cc:791, 580-582
  *   - ids >= table_size are not stored; explicit 0.0 table entries are
  *                                                        sparse-matrix.cc:44, 77
+ *   - subnormal operands, terms and sums are kept: no kernel flushes them, and the build must
+ *     not enable flush-to-zero (-fgpu-flush-denormals-to-zero changes every subnormal result)
+ *   - "bit-identical" covers every output that is not a NaN.  A NaN result is a NaN where the
+ *     reference has one; its sign and payload are the hardware's, and no kernel canonicalises
+ *     them.  The x86 reference generates 0xFFC00000 for inf - inf and for 0 * inf; the MI355X
+ *     was observed to generate 0xFFC00000 for both as well (tests/test_gpu_range_edges.py), but
+ *     only the NaN itself is promised.
  * Summation order: SM_ALGO_PARITY adds the terms of every output in stored
  * (ascending column) order, exactly as the reference does, so results are
  * bit-identical to the reference CPU kernel.  SM_ALGO_XBAND keeps that order for
