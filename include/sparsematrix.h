@@ -210,7 +210,18 @@ SM_API sm_status sm_create_from_dense_index_device(const uint8_t *d_index, int32
 
 /* Additive CSR ingestion (no reference equivalent: the reference cannot encode
  * the north-star sizes).  B is n_rows x n_cols; row_ptr has
- * n_rows+1 entries.  Host pointers, validated on the host. */
+ * n_rows+1 entries.  Host pointers, validated on the host.
+ *
+ * Rows: a row may hold its columns in any order and may repeat a column; B is the sum of
+ * its stored terms, and "the reference's order" for such a row is its stored order.
+ * The layouts that need a row's columns ascending (the band kinds exact, blocked, gather,
+ * band2, cband, gcb; the column sweep; the column-chunked sliced ELL) are not built for a
+ * matrix with a descending step in a row, forced or not: a forced one leaves
+ * sm_info.has_xband == 0, sweep_blocks == 0, ccsell_chunks == 0, and the matrix is served by
+ * the layouts that remain (sliced ELL, merge, the CSR kernels), within the same bound.
+ * Of these only exact, blocked and gather take a row whose columns ascend with repeats; the
+ * others need strictly ascending columns and are not built for it either.  sm_to_dense keeps the last stored of several
+ * repeats; sm_build_ref_stream refuses a matrix with a repeated (row, column). */
 SM_API sm_status sm_create_from_csr(int64_t n_rows, int64_t n_cols, int64_t nnz,
                                     const int32_t *row_ptr, const int32_t *col_idx,
                                     const float *val, int32_t device, sm_matrix **out);
@@ -418,7 +429,10 @@ SM_API sm_status sm_copy_ref_stream(const sm_matrix *m, uint8_t *pos, uint8_t *v
  * 255).  A matrix sm_create_transpose made from a dense-index one, given that one's codebook,
  * uses the ids the index gave the terms instead (equal entries stay apart).
  * A matrix that already holds the encoding is left as it is.  SM_ERR_NOT_SUPPORTED on a matrix
- * built with sm_build_opts.updatable (the stream would go stale).  Not concurrent with
+ * built with sm_build_opts.updatable (the stream would go stale), and on a matrix that stores
+ * a (row, column) more than once: the reference's format comes from a dense index and cannot
+ * hold one (the matrix stays as it was).  Rows with unsorted columns are fine: the encoder
+ * sorts.  Not concurrent with
  * other calls on the matrix.  Additive: the reference cannot hold a matrix without it. */
 SM_API sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t table_size);
 
@@ -435,7 +449,8 @@ SM_API sm_status sm_copy_csr_device(const sm_matrix *m, int32_t *d_row_ptr, int3
 
 /* CopyTo (sparse-matrix.cc:101-137), host output.  NoTrans writes S
  * (s_rows x stride), Trans writes S^T (s_cols x stride); untouched elements
- * are zeroed.  Decoded on the device. */
+ * are zeroed.  Decoded on the device.  A (row, column) stored more than once gets the value
+ * of its last stored term (the products add every one). */
 SM_API sm_status sm_to_dense(const sm_matrix *m, float *out, int32_t stride, sm_trans trans);
 
 /* operator== (sparse-matrix.cc:197-207) on semantic content: shape, stored

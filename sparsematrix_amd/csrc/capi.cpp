@@ -791,6 +791,9 @@ sm_status sm_build_ref_stream(sm_matrix *m, const float *table, int32_t table_si
     if (rc == -2) return fail(SM_ERR_INVALID_ARG, "a value is not in the codebook");
     if (rc == -3) return fail(SM_ERR_NOT_SUPPORTED, "more than 255 distinct values: no uint8 ids");
     if (rc == -4) return fail(SM_ERR_NOT_SUPPORTED, "S rows >= 2^23: the reference's int32 offsets overflow");
+    if (rc == -6)
+        return fail(SM_ERR_NOT_SUPPORTED, "a (row, column) is stored more than once: the reference's "
+                                          "stream comes from a dense index and cannot hold a repeat");
     if (rc != 0) return fail(SM_ERR_INVALID_ARG, "bad codebook");
     // d_term_ids indexes m->table and lives only while no stream is held: from here the stream
     // carries the ids (of whichever codebook was given), so the carried ones go.

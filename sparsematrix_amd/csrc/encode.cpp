@@ -169,6 +169,10 @@ int encode_csr_ref(const int32_t *rp, const int32_t *col, const float *val, int6
                          [](const std::pair<uint64_t, uint8_t> &a, const std::pair<uint64_t, uint8_t> &b) {
                              return a.first < b.first;
                          });
+        // The same (row, column) twice: the reference's stream comes from a dense index and
+        // cannot hold it (equal keys, not gap 0 -- a panel's first entry at 0 has gap 0 too).
+        for (size_t i = 1; i < ent.size(); i++)
+            if (ent[i].first == ent[i - 1].first) return -6;
         const int64_t begin = (int64_t)out.pos.size();
         int64_t prev = 0;
         for (const auto &pe : ent) {

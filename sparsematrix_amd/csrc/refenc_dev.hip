@@ -3,8 +3,9 @@
 // constructor keep, the same bytes encode_csr_ref (encode.cpp) produces on the host.
 //
 // The stream's order is per panel of 256 S columns (= 256 CSR rows), entries row-major in
-// S: by (S row = CSR column, S column in the panel).  Each CSR row is sorted already, so a
-// panel's entries are the merge of its 256 rows -- done here as one device radix sort of
+// S: by (S row = CSR column, S column in the panel).  A panel's entries are the merge of its
+// 256 rows (sorted or not: the keys decide; two equal keys are one (row, column) stored twice,
+// which no dense index gives and the encoder refuses) -- done here as one device radix sort of
 // 64-bit keys (panel, column, row in panel), the panel in the high bits so each panel's
 // entries keep the CSR's [row_ptr[256 p], row_ptr[256 p + 256]) span.  Then per entry the
 // gap to the previous one in its panel gives its bytes (gap > 255: (gap - 1) / 255 filler
@@ -98,10 +99,13 @@ __device__ __forceinline__ int64_t entry_gap(const uint64_t *key, int64_t i, int
     return (int64_t)((k & mask) - prev);
 }
 
-// Bytes of each sorted entry: its filler steps + itself.
+// Bytes of each sorted entry: its filler steps + itself.  Two equal keys -- one (row, column)
+// stored twice -- set *repeat (not gap == 0: a panel's first entry at linear index 0 has that too).
 __global__ __launch_bounds__(256) void refenc_bytes_kernel(int64_t n, const uint64_t *__restrict__ key,
-                                                           int lin_bits, int64_t *__restrict__ bytes) {
+                                                           int lin_bits, int64_t *__restrict__ bytes,
+                                                           int32_t *__restrict__ repeat) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i > 0 && key[i] == key[i - 1]) atomicOr(repeat, 1);
         const int64_t gap = entry_gap(key, i, lin_bits);
         bytes[i] = (gap > kMaxStep ? (gap - 1) / kMaxStep : 0) + 1;
     }
@@ -278,7 +282,8 @@ int encode_csr_ref_device(const int32_t *d_rp, const int32_t *d_col, const float
     }
     RE_TRY(b.alloc(&bytes, nnz));
     RE_TRY(b.alloc(&off, nnz));
-    hipLaunchKernelGGL(refenc_bytes_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, key_s, lin_bits, bytes);
+    // `bad` is still 0 here (a value outside the codebook returned above): it now takes the repeats
+    hipLaunchKernelGGL(refenc_bytes_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, key_s, lin_bits, bytes, bad);
     RE_TRY(hipGetLastError());
     {
         size_t tmp_bytes = 0;
@@ -290,7 +295,9 @@ int encode_csr_ref_device(const int32_t *d_rp, const int32_t *d_col, const float
     int64_t last[2] = {0, 0};
     RE_TRY(hipMemcpyAsync(&last[0], off + nnz - 1, 8, hipMemcpyDeviceToHost, s));
     RE_TRY(hipMemcpyAsync(&last[1], bytes + nnz - 1, 8, hipMemcpyDeviceToHost, s));
+    RE_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
     RE_TRY(hipStreamSynchronize(s));
+    if (h_bad) return -6;   // a repeated (row, column): no stream of the reference's holds it
     const int64_t total = last[0] + last[1];
     uint8_t *pos = nullptr, *vid = nullptr;
     RE_TRY(b.alloc(&pos, total));

@@ -43,6 +43,13 @@ bool xband_build(const int32_t *rp, const int32_t *col, const float *val, int64_
                  int32_t start_rows, bool want_term) {
     if (bits.col < 8 || bits.row < 6 || bits.rank < 2 || bits.col + bits.rank + bits.row != 32)
         return false;
+    // A row's columns must ascend (repeats allowed: they take consecutive ranks of one segment).
+    // The band walk below cannot see a descending step -- its last band ends past n_cols, so
+    // every cursor reaches its row's end -- and would put the smaller column into a later band,
+    // where its offset wraps into the rank and row fields.
+    for (int64_t r = 0; r < n_rows; r++)
+        for (int32_t e = rp[r] + 1; e < rp[r + 1]; e++)
+            if (col[e] < col[e - 1]) return false;
     int32_t br0 = 1 << bits.row;
     while (start_rows > 0 && br0 > start_rows && br0 > 64) br0 /= 2;
     for (int32_t br = br0; br >= 64; br /= 2) {
@@ -84,7 +91,7 @@ static bool xband_build_fixed(const int32_t *rp, const int32_t *col, const float
     };
 
     // Walk the block's terms band by band.  A cursor per row remembers where
-    // the row's next band starts (columns ascend within a row).
+    // the row's next band starts (columns ascend within a row: xband_build checked).
     auto walk = [&](int64_t b, auto &&emit_seg) {
         const int64_t r0 = b * block_rows, r1 = std::min<int64_t>(n_rows, r0 + block_rows);
         std::vector<int32_t> cur((size_t)(r1 - r0));
@@ -98,9 +105,6 @@ static bool xband_build_fixed(const int32_t *rp, const int32_t *col, const float
                 if (c > s) emit_seg(p, (int32_t)(r - r0), s, c);
             }
         }
-        for (int64_t r = r0; r < r1; r++)   // unsorted columns would leave terms behind
-            if (cur[r - r0] != rp[r + 1]) return false;
-        return true;
     };
     // The gather kind lists a band's segments by first column (ties: by row), so
     // the consecutive entries of a chunk -- one wave-instruction of x gathers --
@@ -109,26 +113,24 @@ static bool xband_build_fixed(const int32_t *rp, const int32_t *col, const float
     auto walk_ordered = [&](int64_t b, auto &&emit_seg) {
         if (!col_order) return walk(b, emit_seg);
         std::vector<Seg4> all;
-        const bool ok = walk(b, [&](int64_t p, int32_t rl, int32_t s, int32_t e) {
+        walk(b, [&](int64_t p, int32_t rl, int32_t s, int32_t e) {
             all.push_back(Seg4{(int32_t)p, rl, s, e});
         });
         std::stable_sort(all.begin(), all.end(), [&](const Seg4 &a, const Seg4 &c) {
             return a.p != c.p ? a.p < c.p : col[a.s] < col[c.s];
         });
         for (const Seg4 &g : all) emit_seg((int64_t)g.p, g.rl, g.s, g.e);
-        return ok;
     };
 
     for_blocks([&](int64_t b) {
         std::vector<int32_t> fill((size_t)nb, 0);   // entries used in the open chunk
         int64_t *cnt = &chunks_of[(size_t)(b * nb)];
-        const bool ok = walk_ordered(b, [&](int64_t p, int32_t, int32_t s, int32_t e) {
+        walk_ordered(b, [&](int64_t p, int32_t, int32_t s, int32_t e) {
             const int32_t len = e - s;
             if (len >= bits.max_seg()) { bad[b] = 1; return; }
             if (fill[p] == 0 || fill[p] + len > 64) { cnt[p]++; fill[p] = 0; }
             fill[p] += len;
         });
-        if (!ok) bad[b] = 1;
     });
     for (int64_t b = 0; b < nblk; b++)
         if (bad[b]) return false;

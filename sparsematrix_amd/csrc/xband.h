@@ -61,8 +61,9 @@ struct XbandHost {
 };
 
 // Returns false when the matrix does not fit the layout (a row segment longer
-// than bits.max_seg()-1 inside one band, unsorted columns, bands too dense even
-// for 64-row blocks, or size limits).  The block height starts at 2^bits.row (or
+// than bits.max_seg()-1 inside one band, a row with col[k] < col[k-1] anywhere, bands too
+// dense even for 64-row blocks, or size limits).  A repeated column is taken: the repeats are
+// consecutive terms of one segment, added in stored order.  The block height starts at 2^bits.row (or
 // `start_rows` when smaller and > 0) and halves while a band overflows the
 // kernel's register capacity.  col_order: a band's segments are listed by their
 // first column instead of by row (the gather kind).  want_term: also the slot -> term map

@@ -126,8 +126,58 @@ def uniform_csr(n_rows: int, n_cols: int, per_row: int, seed: int, table=None):
     return rp, cols.reshape(-1).astype(np.int32), val
 
 
+MESSY_ROWS, MESSY_COLS = 4099, 40000
+MESSY_VARIANTS = ("reversed", "shuffled", "repeated", "shuffled_repeated")
+MESSY_LONG = {1234: 300, 3003: 2100}   # past SM_SERIAL_ROW_MAX; past the sell cap and the 2048-term tile
+
+
+def messy_csr(variant: str, seed: int, codebook: bool = True, long_rows: bool = True):
+    """(row_ptr, col_idx, val) of a 4099 x 40000 CSR whose rows are not strictly ascending.
+
+    Base pattern: 8 terms per row from uniform_csr, every 50th row empty, row 1234 of 300 and row
+    3003 of 2100 distinct columns (long_rows=False leaves them at 8: the fixed band kinds take no
+    row with 31 / 63 terms in one band).  4099 rows are two row blocks of 4096 with a partial
+    second one; 40000 columns are three 16384-column bands and five of 8192.  Values from a
+    200-entry table (codebook=False: more than 255 distinct values).  Variants:
+      reversed           every row descending;
+      shuffled           a seeded permutation of every row;
+      repeated           ascending, every 5th row (1, 6, 11, ...) with one column stored twice and
+                         another three times, the repeats adjacent;
+      shuffled_repeated  the previous, every row permuted.
+    The repeats get values of their own, so B[r, c] is their sum."""
+    assert variant in MESSY_VARIANTS, variant
+    rng = np.random.default_rng(seed)
+    table = rng.uniform(-1, 1, 200).astype(np.float32)
+    rp, ci, _ = uniform_csr(MESSY_ROWS, MESSY_COLS, 8, seed=seed + 1, table=table)
+    rows = [ci[rp[r]:rp[r + 1]].astype(np.int64) for r in range(MESSY_ROWS)]
+    for r in range(0, MESSY_ROWS, 50):
+        rows[r] = rows[r][:0]
+    if long_rows:
+        for r, k in MESSY_LONG.items():
+            assert r % 50 != 0 and r % 5 != 1
+            rows[r] = np.sort(rng.choice(MESSY_COLS, k, replace=False))
+    for r in range(MESSY_ROWS):
+        c = rows[r]
+        if "repeated" in variant and r % 5 == 1 and c.size >= 8:
+            c = np.concatenate([c[:2], c[1:2], c[2:6], c[5:6], c[5:]])   # c[1] twice, c[5] three times
+        if variant == "reversed":
+            c = c[::-1]
+        elif variant.startswith("shuffled"):
+            c = rng.permutation(c)
+        rows[r] = c
+    lens = np.array([c.size for c in rows], np.int64)
+    rp2 = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    ci2 = np.concatenate(rows).astype(np.int32)
+    if codebook:
+        va2 = table[rng.integers(0, table.size, ci2.size)]
+    else:
+        va2 = rng.uniform(-1, 1, ci2.size).astype(np.float32)
+    return rp2, ci2, np.ascontiguousarray(va2, np.float32)
+
+
 def skewed_csr(n_rows: int, n_cols: int, lengths: np.ndarray, seed: int):
-    """CSR with the given row lengths (unsorted columns allowed to repeat)."""
+    """CSR with the given row lengths: every row's columns drawn with replacement and sorted
+    ascending, so a row may hold a chance repeat but never a descending step."""
     rng = np.random.default_rng(seed)
     lengths = np.asarray(lengths, np.int64)
     rp = np.zeros(n_rows + 1, np.int64)

@@ -5,7 +5,8 @@
 // with the same table must give the identical stream, panels and table -- NoTrans and
 // Trans, ragged shapes, filler gaps, ids at T - 1, empty matrices and empty panels.
 // Without a table the derived codebook must decode to the same values; out-of-table
-// values, > 255 distinct values and S rows >= 2^23 decline.
+// values, > 255 distinct values and S rows >= 2^23 decline.  Unsorted rows give the sorted rows'
+// stream; a repeated (row, column) declines.
 #include <cstdio>
 #include <cstring>
 #include <random>
@@ -76,6 +77,21 @@ int main() {
         for (int i = 0; i < 256; i++) { col[i] = i; val[i] = (float)i; }
         EncodeResult r;
         CHECK(encode_csr_ref(rp.data(), col.data(), val.data(), 1, 256, nullptr, 0, r) == -3);
+    }
+    // Unsorted rows encode as their sorted form (the encoder sorts); a (row, column) stored twice
+    // declines with -6 -- also at linear index 0 of a panel, where a lone entry has gap 0 too.
+    {
+        const std::vector<int32_t> rp = {0, 3, 3, 5}, sorted = {0, 7, 900, 2, 300}, mixed = {900, 0, 7, 300, 2};
+        const std::vector<float> vs = {1.0f, 2.0f, 3.0f, 4.0f, 5.0f}, vm = {3.0f, 1.0f, 2.0f, 5.0f, 4.0f};
+        EncodeResult a, b, r;
+        CHECK(encode_csr_ref(rp.data(), sorted.data(), vs.data(), 3, 1000, nullptr, 0, a) == 0);
+        CHECK(a.pos.size() > 5 && a.pos[0] == 0);   // fillers, and the first entry at linear index 0
+        const std::vector<float> table(a.table.begin(), a.table.begin() + a.table_size);
+        CHECK(encode_csr_ref(rp.data(), mixed.data(), vm.data(), 3, 1000, table.data(), a.table_size, b) == 0);
+        CHECK(b.pos == a.pos && b.val_id == a.val_id && b.panel_begin == a.panel_begin && b.panel_end == a.panel_end);
+        for (const std::vector<int32_t> &rep : {std::vector<int32_t>{0, 0, 900, 2, 300}, std::vector<int32_t>{900, 7, 900, 2, 300},
+                                                std::vector<int32_t>{0, 7, 900, 300, 300}})
+            CHECK(encode_csr_ref(rp.data(), rep.data(), vs.data(), 3, 1000, nullptr, 0, r) == -6);
     }
     // S rows >= 2^23
     {

@@ -149,6 +149,33 @@ int main() {
             fails++;
         }
     }
+    {   // the builder's rule for a row: strictly ascending columns (gcb.h).  One row of a real
+        // matrix clean, with a descending step (inside a window, across slabs), with a repeat.
+        const int64_t rows = 5000, cols = 40000;
+        auto build = [&](const std::vector<int32_t> &special) {
+            std::vector<int32_t> rp(1, 0), col;
+            std::vector<float> val;
+            for (int64_t r = 0; r < rows; r++) {
+                std::vector<int32_t> cs;
+                for (int i = 0; i < 8; i++) cs.push_back((int32_t)(rng() % (uint64_t)cols));
+                std::sort(cs.begin(), cs.end());
+                cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
+                if (r == 2500) cs = special;
+                for (int32_t x : cs) {
+                    col.push_back(x);
+                    val.push_back((float)(1 + rng() % 1000));
+                }
+                rp.push_back((int32_t)col.size());
+            }
+            GcbHost h;
+            const bool ok = gcb_build(rp.data(), col.data(), val.data(), rows, cols, 14, 2, 1 << 12, h);
+            return ok ? check(rp, col, val, rows, cols, 14, 2, 1 << 12) == 0 : false;
+        };
+        if (!build({5, 20000, 30000})) { printf("FAIL clean row declined\n"); fails++; }
+        if (build({100, 50, 200})) { printf("FAIL descending step accepted\n"); fails++; }
+        if (build({30000, 5, 39999})) { printf("FAIL descending step across slabs accepted\n"); fails++; }
+        if (build({5, 5, 20000, 30000})) { printf("FAIL repeated column accepted\n"); fails++; }
+    }
     if (fails) return 1;
     printf("gcb_asan: ok\n");
     return 0;

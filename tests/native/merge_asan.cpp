@@ -76,7 +76,7 @@ static int check(const std::vector<int32_t> &rp, const std::vector<int32_t> &col
 
 static void csr(std::mt19937_64 &g, int64_t n, int64_t n_cols, const std::vector<int32_t> &lens,
                 std::vector<int32_t> &rp, std::vector<int32_t> &col, std::vector<float> &val, int n_values,
-                bool skew) {
+                bool skew, int order = 0) {   // order 1: rows descending; 2: repeats kept, shuffled
     std::vector<float> vals((size_t)n_values);
     for (int k = 0; k < n_values; ++k) vals[(size_t)k] = (float)(k - n_values / 2) * 0.37f + (k == 0 ? -0.0f : 0.0f);
     rp.assign((size_t)n + 1, 0);
@@ -89,7 +89,9 @@ static void csr(std::mt19937_64 &g, int64_t n, int64_t n_cols, const std::vector
             c.push_back(skew ? (int32_t)((u % 64 < 48 ? u % 97 : u) % (uint64_t)n_cols) : (int32_t)(u % (uint64_t)n_cols));
         }
         std::sort(c.begin(), c.end());
-        c.erase(std::unique(c.begin(), c.end()), c.end());
+        if (order != 2) c.erase(std::unique(c.begin(), c.end()), c.end());
+        if (order == 1) std::reverse(c.begin(), c.end());
+        if (order == 2) std::shuffle(c.begin(), c.end(), g);
         for (int32_t x : c) {
             col.push_back(x);
             val.push_back(vals[(size_t)(g() % (uint64_t)n_values)]);
@@ -122,6 +124,15 @@ int main() {
         l2[4500] = 1;
         csr(g, 9000, 10, l2, rp, col, val, 1, false);
         fails += check(rp, col, val, 10, "single_term");
+    }
+    {   // the staging stream's rule for a row: none.  Descending rows, and shuffled rows with
+        // repeated columns (few columns: many ties), are sorted per slice with ties in CSR order.
+        std::vector<int32_t> lens(20001, 16);
+        lens[777] = 3000;
+        csr(g, 20001, 40000, lens, rp, col, val, 200, false, 1);
+        fails += check(rp, col, val, 40000, "descending");
+        csr(g, 20001, 300, lens, rp, col, val, 200, false, 2);
+        fails += check(rp, col, val, 300, "repeated_shuffled");
     }
     {   // declines: 256 distinct values, columns past 2^24, no terms
         std::vector<int32_t> lens(100, 30);

@@ -123,6 +123,30 @@ int main() {
             }
         }
     }
+    {   // the builder's rule for a row: none.  Ascending, descending and repeated columns all sit in
+        // their lanes in stored order (check compares slot by slot with the CSR).
+        for (int kind = 0; kind < 3; kind++) {
+            const int64_t n_rows = 1000;
+            std::vector<int32_t> rp((size_t)n_rows + 1, 0), col;
+            std::vector<float> val;
+            for (int64_t r = 0; r < n_rows; r++) {
+                std::vector<int32_t> c;
+                const int32_t n = r == 500 ? 300 : (int32_t)(rng() % 20);
+                for (int32_t j = 0; j < n; j++) c.push_back((int32_t)(rng() % 40000));
+                std::sort(c.begin(), c.end());
+                if (kind != 2) c.erase(std::unique(c.begin(), c.end()), c.end());
+                if (kind == 1) std::reverse(c.begin(), c.end());
+                if (kind == 2 && c.size() > 2) c[1] = c[0], c[c.size() - 2] = c[c.size() - 1];
+                for (int32_t x : c) { col.push_back(x); val.push_back((float)(rng() % 97) - 48.0f); }
+                rp[(size_t)r + 1] = (int32_t)col.size();
+            }
+            for (int32_t mx : {16, 2048}) {
+                bad += check(rp, col, val, n_rows, mx);
+                bad += check(rp, col, val, n_rows, mx, 64, 3);
+                bad += check(rp, col, val, n_rows, mx, 0, 1, true);
+            }
+        }
+    }
     printf(bad ? "sell_asan: FAILED\n" : "sell_asan: ok\n");
     return bad ? 1 : 0;
 }

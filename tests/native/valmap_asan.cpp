@@ -66,6 +66,32 @@ Csr random_csr(int64_t n_rows, int64_t n_cols, int per_row, unsigned seed, int e
     return m;
 }
 
+// The same draw with every row's columns kept as repeats where they collide (`repeated`: ascending,
+// not strictly) or reversed (`descending`): the builders' rule for a row's columns.
+Csr messy_csr(int64_t n_rows, int64_t n_cols, int per_row, unsigned seed, bool descending) {
+    std::mt19937 rng(seed);
+    Csr m;
+    m.n_rows = n_rows;
+    m.n_cols = n_cols;
+    m.rp.assign(1, 0);
+    for (int64_t r = 0; r < n_rows; r++) {
+        std::vector<int32_t> c;
+        for (int j = 0; j < per_row; j++) c.push_back((int32_t)(rng() % (uint64_t)n_cols));
+        std::sort(c.begin(), c.end());
+        if (descending) {
+            c.erase(std::unique(c.begin(), c.end()), c.end());
+            std::reverse(c.begin(), c.end());
+        } else if (r % 3 == 0 && c.size() > 2) {
+            c[1] = c[0];                        // a column twice ...
+            c[c.size() - 2] = c[c.size() - 1];  // ... and the last one (three times when per_row == 3)
+        }
+        m.col.insert(m.col.end(), c.begin(), c.end());
+        m.rp.push_back((int32_t)m.col.size());
+    }
+    fill_values(m, rng);
+    return m;
+}
+
 template <class T>
 bool same(const std::vector<T> &a, const std::vector<T> &b) {
     return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
@@ -291,6 +317,38 @@ int main() {
     bad += check_gcb(random_csr(9000, 70001, 40, 4), 14, 2, 1 << 18);
     bad += check_gcb(random_csr(5000, 1000, 5, 5), 14, 2, 1 << 18);
     bad += check_gcb(random_csr(1, 50000, 300, 6), 14, 1, 1 << 18);
+    // Rows that do not strictly ascend.  Repeated columns: the fixed band kinds and the sliced
+    // ELL take them with a map that names every term once; band2, gcb and ccsell decline.  A
+    // descending step: only the sliced ELL (stored order) is built.
+    {
+        const Csr rep = messy_csr(5000, 40000, 8, 21, false), desc = messy_csr(5000, 40000, 8, 22, true);
+        const XbBits exact = xb_bits(kXbExactBandLog2, kXbExactRowsLog2);
+        const XbBits blocked = xb_bits(kXbBlockedBandLog2, kXbBlockedRowsLog2);
+        const struct { XbBits bits; int waves; bool col_order; } kinds[] = {
+            {exact, kXbThreads / 64, false}, {blocked, kXbComputeWaves, false}, {blocked, kXbThreads / 64, true}};
+        for (const auto &k : kinds) {
+            bad += check_xband(rep, k.bits, k.waves, k.col_order);
+            XbandHost xh;
+            if (xband_build(desc.rp.data(), desc.col.data(), desc.val1.data(), desc.n_rows, desc.n_cols, k.bits, k.waves,
+                            xh, k.col_order, 0, true)) {
+                printf("FAIL xband: descending columns accepted\n");
+                bad++;
+            }
+        }
+        for (const Csr *m : {&rep, &desc}) {
+            Band2Host b2;
+            GcbHost gh;
+            CcsellHost ch;
+            if (band2_build(m->rp.data(), m->col.data(), m->val1.data(), m->n_rows, m->n_cols, 1, b2, nullptr, kB2Wide, 1000, true) ||
+                gcb_build(m->rp.data(), m->col.data(), m->val1.data(), m->n_rows, m->n_cols, 14, 1, 1 << 18, gh, true) ||
+                ccsell_build(m->rp.data(), m->col.data(), m->val1.data(), nullptr, m->n_rows, m->n_cols, 12, ch, true, true)) {
+                printf("FAIL band2 / gcb / ccsell: columns not strictly ascending accepted\n");
+                bad++;
+            }
+            bad += check_sell(*m, 16, 0, 1);
+            bad += check_sell(*m, 2048, 1000, 8);
+        }
+    }
     printf(bad ? "valmap_asan: FAILED\n" : "valmap_asan: ok\n");
     return bad ? 1 : 0;
 }

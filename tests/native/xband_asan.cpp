@@ -5,7 +5,8 @@
 // in ascending column order (bands ascend, ranks ascend inside a band), with
 // correct ranks, no row's segment split across chunks, the register capacity
 // respected, padding decoding as dummies, and (gather) a band's chunks in ascending
-// order of their segments' first columns.
+// order of their segments' first columns.  The slot -> term map names every term once.
+// A row with a descending step declines; repeated columns are taken (check_row_rule).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -16,22 +17,13 @@
 
 using namespace smamd;
 
-static int check(XbBits bits, int waves, int64_t n_rows, int64_t n_cols, int per_row,
-                 unsigned seed, bool expect_ok, bool col_order = false) {
-    std::mt19937 rng(seed);
-    std::vector<int32_t> rp(n_rows + 1), col;
-    std::vector<float> val;
-    for (int64_t r = 0; r < n_rows; r++) {
-        std::vector<int32_t> c(per_row);
-        for (auto &v : c) v = (int32_t)(rng() % n_cols);
-        std::sort(c.begin(), c.end());
-        c.erase(std::unique(c.begin(), c.end()), c.end());
-        for (auto v : c) { col.push_back(v); val.push_back((float)(rng() % 1000)); }
-        rp[r + 1] = (int32_t)col.size();
-    }
+// Builds the CSR (with the slot -> term map) and, where the build is expected, decodes it.
+static int verify(XbBits bits, int waves, const std::vector<int32_t> &rp, const std::vector<int32_t> &col,
+                  const std::vector<float> &val, int64_t n_cols, bool expect_ok, bool col_order) {
+    const int64_t n_rows = (int64_t)rp.size() - 1;
     XbandHost xh;
     const bool ok = xband_build(rp.data(), col.data(), val.data(), n_rows, n_cols, bits, waves, xh,
-                                col_order);
+                                col_order, 0, true);
     if (ok != expect_ok) { printf("FAIL build=%d expected %d\n", ok, expect_ok); return 1; }
     if (!ok) return 0;
     if (xh.block_rows > (1 << bits.row) || xh.band_cols != (1 << bits.col)) {
@@ -40,6 +32,8 @@ static int check(XbBits bits, int waves, int64_t n_rows, int64_t n_cols, int per
         printf("FAIL register capacity\n"); return 1; }
     const uint32_t colmask = (1u << bits.col) - 1u, rankmask = (1u << bits.rank) - 1u;
     std::vector<std::vector<std::pair<int32_t, float>>> got(n_rows);
+    std::vector<int> term_seen(col.size(), 0);   // the slot -> term map: every term exactly once
+    if (xh.term.size() != xh.word.size()) { printf("FAIL term map size\n"); return 1; }
     for (int64_t b = 0; b < xh.n_blocks; b++)
         for (int64_t p = 0; p < xh.n_bands; p++) {
             const int64_t c0 = xh.chunk_start[b * xh.n_bands + p];
@@ -55,6 +49,7 @@ static int check(XbBits bits, int waves, int64_t n_rows, int64_t n_cols, int per
                     const uint32_t rank = (w >> bits.col) & rankmask;
                     if (rank == bits.dummy_rank()) {
                         if (xh.val[idx] != 0.0f) { printf("FAIL dummy value\n"); return 1; }
+                        if (xh.term[idx] != -1) { printf("FAIL dummy term\n"); return 1; }
                         continue;
                     }
                     const uint32_t cl = w & colmask;
@@ -69,6 +64,11 @@ static int check(XbBits bits, int waves, int64_t n_rows, int64_t n_cols, int per
                         printf("FAIL rank\n"); return 1; }
                     seen_rows.push_back((int)rl);
                     got[r].push_back({(int32_t)(p * xh.band_cols + cl), xh.val[idx]});
+                    const int32_t t = xh.term[idx];
+                    if (t < rp[r] || t >= rp[r + 1] || col[t] != (int32_t)(p * xh.band_cols + cl) ||
+                        val[t] != xh.val[idx] || t != rp[r] + (int32_t)got[r].size() - 1) {
+                        printf("FAIL term map\n"); return 1; }
+                    term_seen[t]++;
                     if (rank == 0) { cmin = std::min(cmin, cl); cmax = std::max(cmax, cl); }
                 }
                 if (col_order && cmin != 0xFFFFFFFFu) {
@@ -84,7 +84,56 @@ static int check(XbBits bits, int waves, int64_t n_rows, int64_t n_cols, int per
             if (got[r][e - rp[r]].first != col[e] || got[r][e - rp[r]].second != val[e]) {
                 printf("FAIL order row %lld\n", (long long)r); return 1; }
     }
+    for (int n : term_seen)
+        if (n != 1) { printf("FAIL term map coverage\n"); return 1; }
     return 0;
+}
+
+// Random rows of `per_row` draws, sorted; `distinct` drops the repeated columns.
+static int check(XbBits bits, int waves, int64_t n_rows, int64_t n_cols, int per_row,
+                 unsigned seed, bool expect_ok, bool col_order = false, bool distinct = true) {
+    std::mt19937 rng(seed);
+    std::vector<int32_t> rp(n_rows + 1), col;
+    std::vector<float> val;
+    for (int64_t r = 0; r < n_rows; r++) {
+        std::vector<int32_t> c(per_row);
+        for (auto &v : c) v = (int32_t)(rng() % n_cols);
+        std::sort(c.begin(), c.end());
+        if (distinct) c.erase(std::unique(c.begin(), c.end()), c.end());
+        for (auto v : c) { col.push_back(v); val.push_back((float)(1 + rng() % 1000)); }
+        rp[r + 1] = (int32_t)col.size();
+    }
+    return verify(bits, waves, rp, col, val, n_cols, expect_ok, col_order);
+}
+
+// The builder's rule for a row's columns: any col[k] < col[k-1] declines (inside one band, and
+// across bands, where the walk would file the smaller column under a later band and its offset
+// would wrap into the rank and row fields); repeats that otherwise ascend are taken, every term
+// present in stored order.  One long matrix around the given row so blocks and bands are real.
+static int check_row_rule(XbBits bits, int waves, bool col_order) {
+    const int64_t n_rows = 4099, n_cols = 40000;
+    auto build = [&](const std::vector<int32_t> &special, bool expect_ok) {
+        std::mt19937 rng(17);
+        std::vector<int32_t> rp(n_rows + 1), col;
+        std::vector<float> val;
+        for (int64_t r = 0; r < n_rows; r++) {
+            std::vector<int32_t> c(8);
+            for (auto &v : c) v = (int32_t)(rng() % n_cols);
+            std::sort(c.begin(), c.end());
+            c.erase(std::unique(c.begin(), c.end()), c.end());
+            if (r == 0 || r == 2500 || r == n_rows - 1) c = special;
+            for (auto v : c) { col.push_back(v); val.push_back((float)(1 + rng() % 1000)); }
+            rp[r + 1] = (int32_t)col.size();
+        }
+        return verify(bits, waves, rp, col, val, n_cols, expect_ok, col_order);
+    };
+    int bad = 0;
+    bad += build({5, 20000, 30000}, true);                       // clean
+    bad += build({100, 50, 200}, false);                         // descending inside one band
+    bad += build({20000, 5, 30000}, false);                      // descending across bands
+    bad += build({5, 20000, 30000, 29999}, false);               // the last step, inside the last band
+    bad += build({5, 5, 700, 20000, 20000, 20000, 39999, 39999}, true);   // repeats, otherwise ascending
+    return bad;
 }
 
 int main() {
@@ -104,6 +153,9 @@ int main() {
         bad += check(k.bits, k.waves, 5000, 40000, 8, 5, true, co);
         bad += check(k.bits, k.waves, 70000, 1000003, 16, 7, true, co);
         bad += check(k.bits, k.waves, 300, 20000, 400, 6, false, co);   // a row's segment too long for the rank field
+        bad += check(k.bits, k.waves, 5000, 300, 6, 8, true, co, false);    // many repeated columns, one band
+        bad += check(k.bits, k.waves, 9000, 20001, 40, 9, true, co, false); // repeats over several bands
+        bad += check_row_rule(k.bits, k.waves, co);
     }
     printf(bad ? "xband_asan: FAILED\n" : "xband_asan: ok\n");
     return bad ? 1 : 0;
