@@ -227,9 +227,12 @@ SM_API sm_status sm_create_from_csr(int64_t n_rows, int64_t n_cols, int64_t nnz,
                                     const float *val, int32_t device, sm_matrix **out);
 
 /* Same, from device pointers on `device` (copied device-to-device on `stream`
- * and validated by a kernel; synchronises `stream`).  The layout builders run on
- * the host: the columns (and, for the layout that stores them, the values) are
- * copied to the host once, at creation -- 4 + 4 bytes per term over PCIe. */
+ * and validated by a kernel; synchronises `stream`).  The column relabeling, the sorted
+ * sliced ELL, the gathered chunk bands, the balanced bands (band2, cband) and the merge
+ * staging copy are built on the device from the device CSR (sm_build_opts.host_build,
+ * sm_built_on_device).  The other layouts are built on the host: for them the columns (and,
+ * for a layout that stores them, the values) are copied to the host once, at creation --
+ * 4 + 4 bytes per term over PCIe. */
 SM_API sm_status sm_create_from_csr_device(int64_t n_rows, int64_t n_cols, int64_t nnz,
                                            const int32_t *d_row_ptr, const int32_t *d_col_idx,
                                            const float *d_val, int32_t device, sm_stream stream,
@@ -295,10 +298,15 @@ typedef struct sm_build_opts {
                                   2-byte slots, 6 bytes per term) when the values form a codebook
                                   and n_cols <= 2^24; the tile gathers x in column order (R-MAT 24:
                                   1.91 -> 1.68 ms), same bits as without.  0 = never (default)  */
-    int32_t host_build;        /* sm_create_from_csr_device: 0 = auto -- the column relabeling and
-                                  the sorted sliced ELL are built on the device where they are
-                                  the only layouts wanted (builddev.hip; the same bytes as the
-                                  host builders); 1 = always on the host                      */
+    int32_t host_build;        /* sm_create_from_csr_device, sm_create_transpose: 0 = auto -- the
+                                  column relabeling and the sorted sliced ELL are built on the
+                                  device where they are the only layouts wanted, the gathered
+                                  chunk bands and the balanced bands (band2, cband) where they are
+                                  the band kind (builddev*.hip; the same bytes as the host
+                                  builders, sm_layout_digest; sm_built_on_device tells which ran);
+                                  1 = always on the host.  updatable and table_updatable matrices,
+                                  hot_cols and the column sweep keep the host builders: their
+                                  slot -> term maps and given ids are not built on the device  */
     int32_t updatable;         /* 1: the stored values can be replaced in place (sm_set_values,
                                   sm_axpy_values).  No layout decision then reads the values: the
                                   matrix is built as if they took more than 255 bit patterns --
@@ -408,8 +416,18 @@ SM_API sm_status sm_get_info_ex(const sm_matrix *m, sm_info *info, size_t info_b
  * [2] its slots (column words, values), [3] its codebook and the merge path's staging copy
  * (sm_build_opts.merge_stage: column words, offsets, table).  0 for a part not built.  With the
  * gathered chunk bands (SM_LAYOUT_GCB) [1] is their geometry, tile -> band offsets and band
- * start columns, [2] the bands' words.  Synchronises the device. */
+ * start columns, [2] the bands' words.  With the balanced bands (band2, cband) and no sliced
+ * ELL beside them [1] is their geometry (block rows, window, blocks, slabs, slab columns),
+ * tile -> band offsets and band start columns, [2] the bands' entry words, [3] for cband the
+ * layout's copy of the table (256 floats) and its size.  Synchronises the device. */
 SM_API sm_status sm_layout_digest(const sm_matrix *m, uint64_t digest[4]);
+/* Which layouts of `m` the device builders made (0: all built on the host, or none built). */
+#define SM_BUILT_DEV_RELABEL 1u      /* the column relabeling */
+#define SM_BUILT_DEV_SELL 2u         /* the sorted sliced ELL */
+#define SM_BUILT_DEV_GCB 4u          /* the gathered chunk bands */
+#define SM_BUILT_DEV_MERGE_STAGE 8u  /* the merge path's staging copy */
+#define SM_BUILT_DEV_BANDS 16u       /* the balanced bands (band2, cband) */
+SM_API sm_status sm_built_on_device(const sm_matrix *m, uint32_t *mask);
 SM_API int32_t sm_num_rows(const sm_matrix *m);   /* NumRows, sparse-matrix.h:39 */
 SM_API int32_t sm_num_cols(const sm_matrix *m);   /* NumCols, sparse-matrix.h:40 */
 

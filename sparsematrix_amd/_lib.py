@@ -48,7 +48,7 @@ EXPORTS = (
     "sm_multi_last_error", "sm_multi_partition", "sm_multi_unique_id", "sm_multi_create",
     "sm_multi_destroy", "sm_multi_spmv", "sm_multi_spmm", "sm_multi_spmv_batch",
     "sm_multi_allgather", "sm_multi_set_timing", "sm_multi_last_times", "sm_multi_create_with",
-    "sm_debug_seed_handoff", "sm_layout_digest", "sm_sddmm", "sm_copy_csr_device",
+    "sm_debug_seed_handoff", "sm_layout_digest", "sm_built_on_device", "sm_sddmm", "sm_copy_csr_device",
     "sm_set_values", "sm_axpy_values",
     "sm_create_from_csr_ids", "sm_copy_table_device", "sm_copy_term_ids_device", "sm_sddmm_table",
     "sm_set_table", "sm_axpy_table",
@@ -151,6 +151,7 @@ def _declare(L):
         "sm_get_info": ([_vp, C.POINTER(SmInfo)], C.c_int),
         "sm_get_info_ex": ([_vp, C.POINTER(SmInfo), C.c_size_t], C.c_int),
         "sm_layout_digest": ([_vp, C.POINTER(C.c_uint64)], C.c_int),
+        "sm_built_on_device": ([_vp, C.POINTER(C.c_uint32)], C.c_int),
         "sm_num_rows": ([_vp], _i32),
         "sm_num_cols": ([_vp], _i32),
         "sm_copy_ref_stream": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),

@@ -711,6 +711,24 @@ sm_status sm_layout_digest(const sm_matrix *m, uint64_t digest[4]) {
         digest[2] = w.h;
     }
     const SellDev &d = p.sell;
+    const Band2Dev &b2 = p.b2;
+    bool b2_table = false;
+    if (b2.n_blocks > 0 && d.n_slices == 0) {   // balanced bands (xband.h Band2Host), no sliced ELL beside them
+        const int64_t ntile = (int64_t)b2.n_blocks * b2.n_slabs;
+        const bool cb = b2.kind == kXbCband;
+        Fnv f;
+        const int32_t geo[7] = {b2.kind, b2.block_rows, b2.window, b2.n_blocks, b2.n_slabs, b2.slab_cols, b2.slab0_cols};
+        f.add(geo, sizeof(geo));
+        if ((st = fnv_dev(f, b2.d_tile_band, ntile + 1)) != SM_OK) return st;
+        if ((st = fnv_dev(f, b2.d_band_clo, b2.n_bands)) != SM_OK) return st;
+        digest[1] = f.h;
+        // entry words per band: the window tells the geometry (dma3: 30 chunks, wide: 32)
+        const int64_t chunks = b2.window == kB2Wide.window ? kB2Wide.chunks() : kB2Dma3Cb.chunks();
+        Fnv w;
+        if ((st = fnv_dev(w, b2.d_ent, (int64_t)b2.n_bands * chunks * (cb ? 64 : 128))) != SM_OK) return st;
+        digest[2] = w.h;
+        b2_table = cb && b2.d_table;
+    }
     if (d.n_slices > 0) {
         std::vector<int64_t> off((size_t)d.n_slices);
         std::vector<int32_t> len((size_t)d.n_slices);
@@ -739,6 +757,11 @@ sm_status sm_layout_digest(const sm_matrix *m, uint64_t digest[4]) {
         t.add(&d.table_size, 4);
         any = true;
     }
+    if (b2_table) {
+        if ((st = fnv_dev(t, b2.d_table, 256)) != SM_OK) return st;
+        t.add(&b2.table_size, 4);
+        any = true;
+    }
     if (p.d_mstage_w) {
         if ((st = fnv_dev(t, p.d_mstage_w, m->nnz)) != SM_OK) return st;
         if ((st = fnv_dev(t, p.d_mstage_z, m->nnz)) != SM_OK) return st;
@@ -746,6 +769,12 @@ sm_status sm_layout_digest(const sm_matrix *m, uint64_t digest[4]) {
         any = true;
     }
     if (any) digest[3] = t.h;
+    return SM_OK;
+}
+
+sm_status sm_built_on_device(const sm_matrix *m, uint32_t *mask) {
+    if (!m || !mask) return fail(SM_ERR_INVALID_ARG, "null argument");
+    *mask = m->built_on_device;
     return SM_OK;
 }
 

@@ -244,16 +244,43 @@ static sm_status alloc_slab_scratch(sm_matrix *m, BandTiles &d, int64_t n_rows, 
 // stages x -- config 2 34.0-34.6 vs 36.9-37.1 us for the wide geometry with codebook words,
 // 37.9-38.0 vs 38.6-38.7 with 8-byte entries), 4 = dma3, 6 = wide.  dma3
 // bands that would be < 70 % full fall back to wide.
-static sm_status build_band2(sm_matrix *m, Band2Dev &d, int64_t n_rows, int64_t n_cols, int64_t nnz,
-                             const int32_t *rp, const int32_t *col, const float *val, XbKind kind,
-                             int32_t geo_opt, int32_t slabs, bool forced, int32_t slab0_permille = 1000) {
-    const bool dma3 = geo_opt != 6;
-    const B2Geom geom = dma3 ? (kind == kXbCband ? kB2Dma3Cb : kB2Dma3B2) : kB2Wide;
-    const int64_t br = std::min<int64_t>(geom.block_rows, n_rows);
+// The slabs a band2 layout asks band2_build for (sm_build_opts.band_slabs, or about
+// kXbTargetTiles tiles).
+static int32_t band2_want_slabs(int64_t n_rows, int32_t slabs) {
+    const int64_t br = std::min<int64_t>(kB2BlockRows, n_rows);
     const int64_t nblk = (n_rows + br - 1) / br;
     int32_t want = (int32_t)std::max<int64_t>(
         1, std::min<int64_t>(16, (kXbTargetTiles + nblk - 1) / nblk));
     if (slabs > 0) want = std::max(1, std::min(16, slabs));
+    return want;
+}
+
+// The rest of a built band2 / cband layout (its bands already in d_tile_band / d_band_clo /
+// d_ent, by the host or the device builder): the descriptor, the codebook and the slab scratch.
+static sm_status band2_finish(sm_matrix *m, Band2Dev &d, const Band2Host &bh, const std::vector<float> &table,
+                              int64_t n_rows) {
+    d.kind = bh.codebook ? kXbCband : kXbBand2;
+    d.block_rows = bh.block_rows;
+    d.n_blocks = bh.n_blocks;
+    d.n_bands = (int32_t)std::min<int64_t>(bh.n_bands, INT32_MAX);
+    d.n_slabs = bh.n_slabs;
+    d.window = bh.geom.window;
+    d.slab_cols = bh.slab_cols;
+    d.slab0_cols = bh.slab0_cols;
+    if (bh.codebook) {
+        SM_TRY_HIP(dev_upload_table(m->mem, &d.d_table, table.data(), (int32_t)table.size()));
+        d.table_size = (int32_t)table.size();
+    }
+    // One row set per slab: the beta-last hand-off (kernels_band2.hip SM_B2_BL) publishes slab 0's
+    // sums too (the other form writes them into y and leaves the last one unused).
+    return alloc_slab_scratch(m, d, n_rows, bh.n_slabs);
+}
+
+static sm_status build_band2(sm_matrix *m, Band2Dev &d, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                             const int32_t *rp, const int32_t *col, const float *val, XbKind kind,
+                             int32_t geo_opt, int32_t slabs, bool forced, int32_t slab0_permille = 1000) {
+    const bool dma3 = geo_opt != 6;
+    const int32_t want = band2_want_slabs(n_rows, slabs);
     std::vector<float> table;
     std::vector<uint8_t> ids;
     const uint8_t *idp = nullptr;
@@ -280,24 +307,10 @@ static sm_status build_band2(sm_matrix *m, Band2Dev &d, int64_t n_rows, int64_t 
     std::vector<uint8_t>().swap(ids);
     const int64_t band_words = (int64_t)(cb ? 64 : 128) * g.chunks();
     const int64_t ntile = (int64_t)bh.n_blocks * bh.n_slabs;
-    d.kind = cb ? kXbCband : kXbBand2;
-    d.block_rows = bh.block_rows;
-    d.n_blocks = bh.n_blocks;
-    d.n_bands = (int32_t)std::min<int64_t>(bh.n_bands, INT32_MAX);
-    d.n_slabs = bh.n_slabs;
-    d.window = g.window;
-    d.slab_cols = bh.slab_cols;
-    d.slab0_cols = bh.slab0_cols;
     SM_TRY_HIP(m->mem.alloc(&d.d_tile_band, ntile + 1));
     SM_TRY_HIP(m->mem.alloc(&d.d_band_clo, std::max<int64_t>(1, bh.n_bands)));
     SM_TRY_HIP(m->mem.alloc(&d.d_ent, std::max<int64_t>(1, bh.n_bands * band_words)));
-    if (cb) {
-        SM_TRY_HIP(dev_upload_table(m->mem, &d.d_table, table.data(), (int32_t)table.size()));
-        d.table_size = (int32_t)table.size();
-    }
-    // One row set per slab: the beta-last hand-off (kernels_band2.hip SM_B2_BL) publishes slab 0's
-    // sums too (the other form writes them into y and leaves the last one unused).
-    if (const sm_status sts = alloc_slab_scratch(m, d, n_rows, bh.n_slabs)) return sts;
+    if (const sm_status sts = band2_finish(m, d, bh, table, n_rows)) return sts;
     SM_TRY_HIP(hipMemcpy(d.d_tile_band, bh.tile_band_start.data(), (size_t)(ntile + 1) * 4,
                          hipMemcpyHostToDevice));
     if (bh.n_bands > 0) {
@@ -979,22 +992,52 @@ sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell) {
         else if (rc == 0) {
             st = gcb_finish(m, meta);
             dev_done = st == SM_OK;
+            if (dev_done) m->built_on_device |= SM_BUILT_DEV_GCB;
         } else {   // declined: nothing of the attempt stays
             m->mem.release_since(mark);
             m->plan.gcb = GcbDev();
+        }
+    }
+    // The balanced bands on the device (builddev_band2.hip; config 2: 0.41 s on the host path),
+    // with upload_xband's arguments.  Declined (a row's columns not strictly ascending, size
+    // limits, bands under 70 % full, scratch out of memory): the host path below decides -- the
+    // blocked kind or none, as before.  A band matrix wants no sliced ELL; one that wants the
+    // unsegmented sliced ELL beside its bands keeps the host path.
+    const XbKind b2kind = xband ? xband_kind_setting(m) : kXbExact;
+    if (dev_ok && xband && (b2kind == kXbBand2 || b2kind == kXbCband) && m->opts.relabel != 1 &&
+        (m->opts.band_tall == 0 || m->opts.band_tall == 4 || m->opts.band_tall == 6) &&
+        !(exact_sell && want_exact_sell(m))) {
+        hipError_t eb = hipSuccess;
+        const int32_t p0 = m->opts.band_slab0_permille > 0 ? m->opts.band_slab0_permille : kB2Slab0Permille;
+        Band2Host meta;
+        std::vector<float> table;
+        const size_t mark = m->mem.mark();
+        const int rc = devbuild_band2(m, b2kind, m->opts.band_tall, band2_want_slabs(n_rows, m->opts.band_slabs),
+                                      kind_forced(m), p0, meta, table, s, eb);
+        if (rc < 0) st = hip_fail(eb, "device band2 builder");
+        else if (rc == 0) {
+            st = band2_finish(m, m->plan.b2, meta, table, n_rows);
+            dev_done = st == SM_OK;
+            if (dev_done) m->built_on_device |= SM_BUILT_DEV_BANDS;
+        } else {   // declined: nothing of the attempt stays
+            m->mem.release_since(mark);
+            m->plan.b2 = Band2Dev();
         }
     }
     if (dev_ok && !xband) {
         hipError_t eb = hipSuccess;
         int rc = 0;
         if (want_relabel_size(m)) rc = devbuild_relabel(m, m->opts.relabel != 1, s, eb);
+        uint32_t built = rc == 0 && m->plan.n_relabel > 0 ? SM_BUILT_DEV_RELABEL : 0;
         if (rc == 0 && !want_ccsell(m)) {
             if (want_sell(m)) {
                 const int32_t max_len = m->opts.sell_max_len > 0 ? m->opts.sell_max_len : kSellMaxLen;
                 rc = devbuild_sell(m, max_len, m->opts.sell_codebook != 0, s, eb);
+                if (rc == 0 && m->plan.sell.n_slices > 0) built |= SM_BUILT_DEV_SELL;
             }
             dev_done = rc == 0;
         }
+        if (dev_done) m->built_on_device |= built;
         if (rc != 0) st = hip_fail(eb, "device layout builder");
     }
     // The merge path's staging copy (sm_build_opts.merge_stage) after a device build too
@@ -1002,10 +1045,12 @@ sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell) {
     if (st == SM_OK && dev_done && want_merge_stage(m)) {
         hipError_t eb = hipSuccess;
         if (devbuild_merge_stage(m, s, eb) < 0) st = hip_fail(eb, "device merge staging builder");
+        else if (m->plan.d_mstage_w) m->built_on_device |= SM_BUILT_DEV_MERGE_STAGE;
     }
     const bool maybe_sell = m->opts.sell != 0 && nnz > 0;
     const bool maybe_xsell = exact_sell && nnz > 0 && n_rows > 0 && (m->opts.exact_sell == 1 || (m->opts.exact_sell == 0 && m->from_index));
-    // The band / sell builders run on the host (band2.cpp, xband.cpp, sell.cpp): the
+    // The other band kinds, and whatever the device builders declined or the options keep from
+    // them, are built on the host (band2.cpp, xband.cpp, sell.cpp): the
     // columns come down for any of them, the values only for the layout that stores
     // them (4 + 4 bytes per term over PCIe once, at creation).
     if (st == SM_OK && !dev_done &&

@@ -392,6 +392,11 @@ int encode_csr_ref_device(const int32_t *d_rp, const int32_t *d_col, const float
 // upload_sell build on the host.  0 built or declined as the host would, -5 HIP error (err).
 int devbuild_relabel(sm_matrix *m, bool check_skew, hipStream_t s, hipError_t &err);
 int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, hipError_t &err);
+// The codebook of a device value array (builddev.hip), as codebook_ids derives it: `table` in
+// first-occurrence order, d_ids[e] (n bytes on the device) the id of value e.  0 built, 1 more
+// than 255 distinct bit patterns, -5 HIP error (err).
+int devbuild_codebook(const float *d_val, int64_t n, std::vector<float> &table, uint8_t *d_ids, hipStream_t s,
+                      hipError_t &err);
 // The merge path's staging stream (merge_stage_build's bytes) from the device CSR and the
 // plan's slice corners: 0 built, 1 declined as the host would, < 0 on a HIP error (err).
 int devbuild_merge_stage(sm_matrix *m, hipStream_t s, hipError_t &err);
@@ -424,6 +429,17 @@ int exact_algo(const sm_matrix *m, bool x16);
 struct GcbHost;
 int devbuild_gcb(sm_matrix *m, int rows_log2, int32_t n_slabs, int32_t window, GcbHost &meta, hipStream_t s,
                  hipError_t &err);
+// The balanced bands (builddev_band2.hip): the bytes build_band2 has band2_build produce -- the
+// geometry by `geo_opt` (sm_build_opts.band_tall: dma3 first unless 6, wide where dma3's bands
+// would be under 70 % full and not `forced`), codebook words for `kind` kXbCband where the values
+// take at most 255 bit patterns (`table`: the codebook) -- into m->plan.b2's d_tile_band,
+// d_band_clo and d_ent, the geometry in `meta` (its vectors stay empty).  0 built, 1 declined as
+// build_band2 would, or because a development knob is set or the scratch does not fit the device
+// (the caller drops what was allocated till then: DevMem::release_since), < 0 on a HIP error (err)
+// or a builder inconsistency.
+struct Band2Host;
+int devbuild_band2(sm_matrix *m, int32_t kind, int32_t geo_opt, int32_t n_slabs, bool forced, int32_t slab0_permille,
+                   Band2Host &meta, std::vector<float> &table, hipStream_t s, hipError_t &err);
 // The CSR of B^T (transpose_dev.hip) from the device CSR of B (n_rows x n_cols, validated): row c
 // holds column c's terms by ascending source row, equal rows in stored order; values bit for
 // bit.  t_rp: n_cols + 1, t_col / t_val: nnz, on the same device.  Synchronises `s`; frees its
@@ -488,6 +504,7 @@ struct sm_matrix {
     // Every device buffer the matrix keeps (the raw d_* pointers here and in `plan` point into
     // it); mem.bytes is sm_info.device_bytes.  ~sm_matrix frees them all.
     smamd::DevMem mem;
+    uint32_t built_on_device = 0;              // SM_BUILT_DEV_* of the layouts the device builders made
     ~sm_matrix();
     // Reference encoding (only for matrices built by sm_create_from_dense_index).
     bool has_ref = false;

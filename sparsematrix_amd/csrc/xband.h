@@ -168,6 +168,11 @@ bool band2_build(const int32_t *row_ptr, const int32_t *col, const float *val, i
                  int64_t n_cols, int32_t n_slabs, Band2Host &out, const uint8_t *ids = nullptr,
                  B2Geom geom = kB2Wide, int32_t slab0_permille = 1000, bool want_term = false);
 
+// True where a development knob of the builder is in force (-DSM_DEV builds with SM_B2_BAL or
+// SM_B2_TAB4 set, or a build with SM_DEV_B2_WINDOW): the knobs are host-only, so the device
+// builder (builddev_band2.hip) declines and the host builder serves the matrix.
+bool band2_dev_knobs_set();
+
 // Codebook of a value array: table[ids[e]] has the bits of val[e] for every e; false
 // when there are more than 255 distinct bit patterns (table then undefined).
 bool codebook_ids(const float *val, int64_t n, std::vector<float> &table, std::vector<uint8_t> &ids);

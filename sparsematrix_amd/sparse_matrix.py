@@ -294,10 +294,19 @@ class SparseMatrix:
 
     def layout_digest(self) -> tuple:
         """sm_layout_digest: FNV-1a digests of the relabeling, the sliced ELL's structure, its
-        slots and its codebook (0 where not built)."""
+        slots and its codebook, or of a band layout's geometry, entries and table (0 where not
+        built)."""
         d = (C.c_uint64 * 4)()
         check(self._L.sm_layout_digest(self._require(), d), "sm_layout_digest")
         return tuple(int(v) for v in d)
+
+    def built_on_device(self) -> int:
+        """sm_built_on_device: which layouts the device builders made -- 1 the column relabeling,
+        2 the sliced ELL, 4 the gathered chunk bands, 8 the merge staging copy, 16 the balanced
+        bands (band2, cband); 0 when the host builders made them all."""
+        mask = C.c_uint32(0)
+        check(self._L.sm_built_on_device(self._require(), C.byref(mask)), "sm_built_on_device")
+        return int(mask.value)
 
     @property
     def n_rows(self) -> int:
