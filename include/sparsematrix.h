@@ -44,7 +44,11 @@
  * Operands: any 4-byte aligned x / y / X / Y / a / c and any ld >= the row length; placement
  * only selects the kernel (band layouts need x at 16 bytes, the row-panel SpMM ld % 4 == 0 and
  * X, Y at 16 bytes, SM_ALGO_MFMA 8 bytes), and nothing outside y[0, n) or inside the padding
- * columns [n_rhs, ld) is ever written ("Operand placement").
+ * columns [n_rhs, ld) is ever written ("Operand placement").  Size selects the
+ * kernel in the same way: the gather-pipelined row-panel SpMM and SM_ALGO_MFMA form 32-bit byte
+ * offsets, so they run only with X and the term arrays under 4 GiB (n_cols * ldx * 4 and
+ * nnz * 4 bytes, each below 0xFFFFFFF0); past either limit the SpMM runs the plain row-panel
+ * kernel (the same bits) and SM_ALGO_MFMA returns SM_ERR_NOT_SUPPORTED.
  *
  * Concurrency: calls on one matrix from several streams or threads are correct;
  * SpMVs that use the matrix's scratch take turns on the device.
@@ -112,8 +116,10 @@ typedef enum sm_algo {
                              (v_mfma_f32_16x16x4_f32, four terms per step), one fused
                              multiply-add per term: within the sum|terms| bound, not
                              bit-identical; X must be finite (a non-finite X row makes
-                             the tile's other outputs NaN).  SM_ERR_NOT_SUPPORTED for
-                             other shapes and for SpMV.                                */
+                             the tile's other outputs NaN).  X and the term arrays under
+                             4 GiB (n_cols * ldx * 4 and nnz * 4 bytes, each below
+                             0xFFFFFFF0).  SM_ERR_NOT_SUPPORTED otherwise, for other
+                             shapes and for SpMV.                                      */
     SM_ALGO_MERGE = 9     /* SpMV by merge path (Merrill & Garland): every workgroup and
                              thread an equal share of rows + terms, rows cut anywhere.
                              A row inside one thread's share is summed in stored order

@@ -1055,9 +1055,10 @@ sm_status sm_spmm(const sm_matrix *m, int32_t n_rhs, float alpha, const float *X
     }
     if (algo == SM_ALGO_MFMA) {   // the matrix-core SpMM (spmm_mfma.hip)
         if (n_rhs != 32 || ldx % 2 || ldy % 2 || ((uintptr_t)X % 8) || ((uintptr_t)Y % 8) ||
-            (uint64_t)m->n_cols * (uint64_t)ldx * 4u >= 0xFFFFFFF0ull)
+            (uint64_t)m->n_cols * (uint64_t)ldx * 4u >= 0xFFFFFFF0ull ||
+            (uint64_t)m->nnz * 4u >= 0xFFFFFFF0ull)
             return fail(SM_ERR_NOT_SUPPORTED, "SM_ALGO_MFMA needs n_rhs = 32, even ldx/ldy, 8-byte "
-                        "aligned X/Y and X under 4 GiB");
+                        "aligned X/Y, and X and the term arrays under 4 GiB");
         e = launch_spmm_mfma(n, m->d_row_ptr, m->d_col, m->d_val, (int32_t)m->nnz, X, ldx, m->n_cols,
                              Y, ldy, alpha, beta, s);
         e = after_launch(e, s, "sm_spmm mfma");

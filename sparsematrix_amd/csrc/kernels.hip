@@ -339,7 +339,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t panel_rsrc(const void *base, u
 // X-row gathers are in flight together -- branch-free range-checked buffer loads,
 // padded slots sent past the range -- and the terms are added in stored order
 // (padded slots skipped by a select, so the sum is bit-identical).  Requires X
-// (x_rows * ldx floats) under 4 GiB.
+// (x_rows * ldx floats) and the term arrays col / val (nnz elements each) under 4 GiB:
+// x_rows * ldx * 4 < 0xFFFFFFF0 and nnz * 4 < 0xFFFFFFF0 (32-bit byte offsets into all three).
 template <int G>
 __global__ __launch_bounds__(256) void spmm_rowpanel2_kernel(
     int32_t n, int32_t nrhs, const int32_t *__restrict__ rp, const int32_t *__restrict__ col,
@@ -617,11 +618,13 @@ hipError_t launch_spmm_rowpanel(int32_t n, int32_t nrhs, const int32_t *rp, cons
     int G = 1;
     while (4 * G < nrhs) G <<= 1;
     const unsigned grid = blocks_for((int64_t)n * G);
-    // The gather-pipelined kernel while its X descriptor can span X (< 4 GiB) and a
-    // group's gathers fit the registers (G <= 16, i.e. N <= 64); allow_pipelined =
-    // false (sm_spmm with SM_ALGO_VECTOR) keeps the one-group-at-a-time kernel.
+    // The gather-pipelined kernel while its descriptors can span X and the term arrays
+    // (each < 4 GiB: it forms 32-bit byte offsets into col / val as well) and a group's
+    // gathers fit the registers (G <= 16, i.e. N <= 64); allow_pipelined = false (sm_spmm
+    // with SM_ALGO_VECTOR) keeps the one-group-at-a-time kernel, which gives the same bits.
     const bool pipelined = allow_pipelined && G <= 16 &&
-                           (uint64_t)x_rows * (uint64_t)ldx * 4u < 0xFFFFFFF0ull;
+                           (uint64_t)x_rows * (uint64_t)ldx * 4u < 0xFFFFFFF0ull &&
+                           (uint64_t)nnz * 4u < 0xFFFFFFF0ull;
 #define SM_PANEL(GG)                                                                         \
     case GG:                                                                                 \
         if (pipelined)                                                                       \

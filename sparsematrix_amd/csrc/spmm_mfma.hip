@@ -211,7 +211,9 @@ hipError_t launch_spmm_mfma(int32_t n, const int32_t *rp, const int32_t *col, co
                             int32_t nnz, const float *X, int64_t ldx, int64_t x_rows, float *Y,
                             int64_t ldy, float alpha, float beta, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    if ((uint64_t)x_rows * (uint64_t)ldx * 4u >= 0xFFFFFFF0ull || ldx % 2 || ldy % 2 ||
+    // 32-bit byte offsets into X and into col / val: each under 4 GiB
+    if ((uint64_t)x_rows * (uint64_t)ldx * 4u >= 0xFFFFFFF0ull ||
+        (uint64_t)nnz * 4u >= 0xFFFFFFF0ull || ldx % 2 || ldy % 2 ||
         ((uintptr_t)X % 8) || ((uintptr_t)Y % 8))
         return hipErrorInvalidValue;
     const int64_t waves = ((int64_t)n + 15) / 16;
