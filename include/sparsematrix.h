@@ -328,7 +328,8 @@ typedef struct sm_build_opts {
                                   SM_ERR_NOT_SUPPORTED on such a matrix (the stream would go
                                   stale), so SM_ALGO_NATIVE stays unavailable.  0 (default):
                                   nothing changes -- the same layouts, bytes and digests       */
-    int32_t table_updatable;   /* 1: the table of a table matrix (sm_create_from_csr_ids, and
+    int32_t table_updatable;   /* 1: the table of a table matrix (sm_create_from_csr_ids, its
+                                  _device form, sm_create_quantized, and
                                   sm_create_transpose of one) can be replaced in place
                                   (sm_set_table, sm_axpy_table).  Every layout that holds values
                                   then takes its codebook form with the GIVEN ids and the GIVEN
@@ -401,6 +402,97 @@ SM_API sm_status sm_create_from_csr_ids(int64_t n_rows, int64_t n_cols, int64_t 
                                         const uint8_t *ids, const float *table, int32_t table_size,
                                         int32_t device, const sm_build_opts *opts /* NULL: defaults */,
                                         sm_matrix **out);
+/* sm_create_from_csr_ids from device pointers on `device` (all five arrays; ids of any alignment):
+ * the CSR arrays are copied device to device on `stream`, one kernel writes the stored values
+ * val[e] = table[ids[e]] (a bit copy) and finds an id >= table_size (SM_ERR_INVALID_MATRIX), the
+ * ids and the table are copied device to device, and the tail of sm_create_from_csr_device_ex
+ * validates the CSR and builds the layouts.  Synchronises `stream`.  The argument checks are the
+ * host constructor's and run before any device work; in addition opts->updatable = 1 is
+ * SM_ERR_INVALID_ARG here (a table matrix takes new values through its table).
+ * The result is the matrix sm_create_from_csr_ids builds from the same arrays on the host with the
+ * same options: sm_equal, sm_layout_digest, sm_info (device_bytes aside), every product of every
+ * sm_algo, sm_copy_table_device and sm_copy_term_ids_device, bit for bit.
+ * Without opts->table_updatable the layouts are built where sm_create_from_csr_device_ex builds
+ * them from the expanded values (the device builders where they apply; sm_built_on_device reports
+ * the same mask).  With opts->table_updatable = 1 the host builders are needed and take the given
+ * ids and table: the ids (1 byte per term) and the table are copied to the host once, at
+ * creation; the other layouts' downloads are those of sm_create_from_csr_device. */
+SM_API sm_status sm_create_from_csr_ids_device(int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                               const int32_t *d_row_ptr, const int32_t *d_col_idx,
+                                               const uint8_t *d_ids, const float *d_table,
+                                               int32_t table_size, int32_t device, sm_stream stream,
+                                               const sm_build_opts *opts /* NULL: defaults */,
+                                               sm_matrix **out);
+
+/* ---- quantising the stored values: 1-D k-means (Lloyd) on the device ---------------------------
+ * The "quantise" step of prune -> quantise -> fine-tune: from the stored fp32 values of any matrix
+ * (m->d_val in CSR order, whatever constructor made it) to an (ids, table) pair with T <= 255
+ * entries, and from there to a table matrix.  The matrix is only read.  The two step calls
+ * allocate their own scratch and synchronise `stream`: they are not meant for graph capture.
+ * table_size must be in [1, 255] (SM_ERR_INVALID_ARG, checked before the matrix is looked at).
+ *
+ * sm_quantize_assign: ids[e] = the nearest entry of `table` (T floats on the device, any 4-byte
+ * alignment) to val[e]; d_ids: nnz bytes on the device, any alignment; nothing outside
+ * ids[0, nnz) is written.  nnz == 0 launches nothing.  The rule, in this order:
+ *   1. The candidates are formed from the table: NaN entries are dropped; the rest are compared
+ *      as floats, so -0.0 = +0.0; each distinct value is represented by its lowest t.
+ *   2. For a value v, lo is the greatest candidate <= v and hi the least candidate > v.
+ *   3. If only one of them exists, it is chosen.
+ *   4. If both exist, dl = fl32(v - lo) and dh = fl32(hi - v).  lo is chosen, unless dh < dl, or
+ *      dh == dl and t_hi < t_lo.
+ *   5. A NaN v, or a table with no candidate at all, gives id 0.
+ * This is the real-number nearest entry whenever the two distances differ by more than one fp32
+ * rounding (each of dl, dh carries at most one); nearer than that, either neighbour may be chosen
+ * -- always the same one.
+ *
+ * sm_quantize_update: one Lloyd update from given ids, table[t] <- the mean of the values with id
+ * t.  d_ids: nnz bytes, any alignment; d_table: T floats, in: the old table, out: the new one;
+ * d_counts: T int32 or NULL; d_sse: one double (8-byte aligned) or NULL.  Deterministic: no
+ * atomics, the launch geometry a function of nnz alone, every operation below one IEEE double
+ * operation, round to nearest:
+ *   1. Chunk k holds the terms [2048 k, 2048 (k+1)) in CSR order.  p[k][t] = the sum of
+ *      (double)val[e] over the chunk's terms with id t, added in ascending e, one add each, from
+ *      +0.0; c[k][t] their number.
+ *   2. S[t] = p[0][t], p[1][t], ... added in ascending k, one add each, from +0.0; n[t] the sum of
+ *      the c[k][t].
+ *   3. n[t] > 0: table[t] = (float)(S[t] / (double)n[t]).  Otherwise table[t] keeps its bits: an
+ *      empty cluster keeps its entry.
+ *   4. counts[t] = n[t].
+ *   5. With old_table the table as it was on entry: q[k] = the sum over the chunk's terms of
+ *      d * d, d = (double)val[e] - (double)old_table[id_e] (the square rounded once), added in
+ *      ascending e from +0.0; sse = q[0], q[1], ... added in ascending k from +0.0.
+ * An id >= T is SM_ERR_INVALID_MATRIX, found by the pass and reported after the synchronise (the
+ * table, counts and sse hold no meaning then).  nnz == 0: the table is unchanged, counts are 0
+ * and sse is 0.0.
+ *
+ * sm_create_quantized: a new, independent table matrix with src's pattern whose ids and table
+ * come from `iters` Lloyd steps on src's stored values; `src` is untouched and may be any matrix
+ * (an updatable one is the common case).  iters < 0 is SM_ERR_INVALID_ARG; a stored value that is
+ * NaN or Inf is SM_ERR_INVALID_MATRIX (the pass that finds the least and greatest value finds it;
+ * it runs also when d_init is given).
+ *   Start: d_init (T floats on the device), or NULL for the linear table between lo and hi, the
+ *   least and greatest stored value, a zero bound counting as +0.0, computed on the host:
+ *     table[t] = (float)((double)lo + ((double)hi - (double)lo) * ((double)t / (double)(T - 1))),
+ *     T = 1: table[0] = (float)(((double)lo + (double)hi) / 2).
+ *   Steps: `iters` times assign, then update (the kernels of the two calls above, so ids and
+ *   table are bit for bit what those calls give, without their allocations and synchronises);
+ *   one last assign, so the ids are those of the final table; then sm_create_from_csr_ids_device on src's own device row_ptr / col_idx,
+ *   the ids and the table, with `opts` (table_updatable is honoured; updatable = 1 is
+ *   SM_ERR_INVALID_ARG).
+ * The result may hold fewer distinct values than T (empty clusters keep their entry); nnz == 0
+ * gives an empty table matrix with the starting table (all zeros for the linear one).
+ * Synchronises `stream`.  Scratch while it runs: 1 byte per term and, with iters > 0, 12 bytes per
+ * 2048 terms and table slot (ceil(nnz / 2048) * 256 * 12 bytes). */
+SM_API sm_status sm_quantize_assign(const sm_matrix *m, const float *d_table, int32_t table_size,
+                                    uint8_t *d_ids, sm_stream stream);
+SM_API sm_status sm_quantize_update(const sm_matrix *m, const uint8_t *d_ids, int32_t table_size,
+                                    float *d_table /* in: old, out: new */,
+                                    int32_t *d_counts /* T, may be NULL */,
+                                    double *d_sse /* 1, may be NULL */, sm_stream stream);
+SM_API sm_status sm_create_quantized(const sm_matrix *src, int32_t table_size, int32_t iters,
+                                     const float *d_init /* T floats on the device, or NULL: linear */,
+                                     const sm_build_opts *opts, sm_stream stream, sm_matrix **out);
+
 /* The current table (T floats) / the terms' ids (nnz bytes, CSR order) of a table matrix into
  * buffers on its device, asynchronous on `stream`.  SM_ERR_NOT_SUPPORTED on any other matrix. */
 SM_API sm_status sm_copy_table_device(const sm_matrix *m, float *d_table, sm_stream stream);

@@ -52,6 +52,7 @@ EXPORTS = (
     "sm_set_values", "sm_axpy_values",
     "sm_create_from_csr_ids", "sm_copy_table_device", "sm_copy_term_ids_device", "sm_sddmm_table",
     "sm_set_table", "sm_axpy_table",
+    "sm_create_from_csr_ids_device", "sm_quantize_assign", "sm_quantize_update", "sm_create_quantized",
 )
 
 SM_UNIQUE_ID_BYTES = 128
@@ -167,6 +168,11 @@ def _declare(L):
         "sm_axpy_values": ([_vp, _f32, _vp, C.c_int, _vp], C.c_int),
         "sm_create_from_csr_ids": ([_i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32,
                                     C.POINTER(SmBuildOpts), C.POINTER(_vp)], C.c_int),
+        "sm_create_from_csr_ids_device": ([_i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp,
+                                           C.POINTER(SmBuildOpts), C.POINTER(_vp)], C.c_int),
+        "sm_quantize_assign": ([_vp, _vp, _i32, _vp, _vp], C.c_int),
+        "sm_quantize_update": ([_vp, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
+        "sm_create_quantized": ([_vp, _i32, _i32, _vp, C.POINTER(SmBuildOpts), _vp, C.POINTER(_vp)], C.c_int),
         "sm_copy_table_device": ([_vp, _vp, _vp], C.c_int),
         "sm_copy_term_ids_device": ([_vp, _vp, _vp], C.c_int),
         "sm_sddmm_table": ([_vp, _i32, _f32, _vp, _i64, _vp, _i64, _f32, _vp, C.c_int, _vp], C.c_int),

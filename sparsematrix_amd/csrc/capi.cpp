@@ -616,6 +616,212 @@ sm_status sm_create_transpose(const sm_matrix *src, const sm_build_opts *opts, s
     return SM_OK;
 }
 
+// A table matrix from device arrays, the arguments checked and `device` current: the CSR arrays
+// copied, the values expanded from (ids, table) by a kernel that also validates the ids, then
+// the device-CSR constructors' tail (as sm_create_transpose hands a table matrix on).  A
+// table_updatable result needs the ids and the table on the host for the layout builders.
+static sm_status create_from_ids_device(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t *d_rp,
+                                        const int32_t *d_col, const uint8_t *d_ids, const float *d_table,
+                                        int32_t table_size, int32_t device, hipStream_t s, const sm_build_opts *opts,
+                                        sm_matrix **out) {
+    auto m = new_matrix(device, opts);
+    set_shape(m.get(), n_rows, n_cols, nnz);
+    sm_status st = alloc_csr(m.get());
+    if (st != SM_OK) return st;
+    int32_t flag = 0;
+    hipError_t e = hipSuccess;
+    {
+        DevScratch tmp;
+        int32_t *d_flag = nullptr;
+        e = tmp.alloc(&d_flag, 1);
+        if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(m->d_row_ptr, d_rp, (size_t)(n_rows + 1) * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && nnz) e = hipMemcpyAsync(m->d_col, d_col, (size_t)nnz * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = launch_expand_ids(nnz, d_ids, d_table, table_size, m->d_val, d_flag, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) return hip_fail(e, "sm_create_from_csr_ids_device");
+    if (flag) return fail(SM_ERR_INVALID_MATRIX, "an id is >= table_size %d", table_size);
+    st = alloc_table(m.get(), nullptr, table_size);
+    if (st != SM_OK) return st;
+    e = hipStreamSynchronize(nullptr);   // alloc_table zeroed the table on the default stream
+    if (e == hipSuccess && table_size > 0)
+        e = hipMemcpyAsync(m->d_tab, d_table, (size_t)table_size * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(m->d_tab_ids, d_ids, (size_t)nnz, hipMemcpyDeviceToDevice, s);
+    std::vector<uint8_t> h_ids;
+    std::vector<float> h_tab;
+    if (e == hipSuccess && m->opts.table_updatable) {   // 1 byte per term and the table come down once
+        h_ids.resize((size_t)nnz);
+        h_tab.resize(256);
+        e = hipStreamSynchronize(s);
+        if (e == hipSuccess && nnz) e = hipMemcpy(h_ids.data(), m->d_tab_ids, (size_t)nnz, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(h_tab.data(), m->d_tab, 256 * sizeof(float), hipMemcpyDeviceToHost);
+        m->build_ids = h_ids.data();
+        m->build_table = h_tab.data();
+    }
+    st = e == hipSuccess ? finish_from_device_csr(m.get(), s, true) : hip_fail(e, "sm_create_from_csr_ids_device (table)");
+    m->build_ids = nullptr;
+    m->build_table = nullptr;
+    if (st != SM_OK) {
+        m.reset();
+        (void)hipGetLastError();   // a failed allocation leaves no sticky error behind
+        return st;
+    }
+    *out = m.release();
+    return SM_OK;
+}
+
+// What the two device table constructors refuse beyond check_opts(opts, true).
+static sm_status check_table_opts(const sm_build_opts *opts) {
+    const sm_status st = check_opts(opts, true);
+    if (st != SM_OK) return st;
+    if (resolve_opts(opts).updatable)
+        return fail(SM_ERR_INVALID_ARG, "updatable: a table matrix takes new values through its table (table_updatable)");
+    return SM_OK;
+}
+
+sm_status sm_create_from_csr_ids_device(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t *d_row_ptr,
+                                        const int32_t *d_col_idx, const uint8_t *d_ids, const float *d_table,
+                                        int32_t table_size, int32_t device, sm_stream stream,
+                                        const sm_build_opts *opts, sm_matrix **out) {
+    if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    sm_status st = check_table_opts(opts);
+    if (st != SM_OK) return st;
+    st = check_sizes(n_rows, n_cols, nnz);
+    if (st != SM_OK) return st;
+    if (!d_row_ptr || (nnz > 0 && (!d_col_idx || !d_ids))) return fail(SM_ERR_INVALID_ARG, "null CSR array");
+    if (table_size < 0 || table_size > 255 || (nnz > 0 && table_size < 1))
+        return fail(SM_ERR_INVALID_ARG, "table_size %d not in [1, 255]", table_size);
+    if (table_size > 0 && !d_table) return fail(SM_ERR_INVALID_ARG, "null table");
+    st = check_device(device);
+    if (st != SM_OK) return st;
+    DeviceGuard g(device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    return create_from_ids_device(n_rows, n_cols, nnz, d_row_ptr, d_col_idx, d_ids, d_table, table_size, device,
+                                  (hipStream_t)stream, opts, out);
+}
+
+sm_status sm_quantize_assign(const sm_matrix *m, const float *d_table, int32_t table_size, uint8_t *d_ids,
+                             sm_stream stream) {
+    if (table_size < 1 || table_size > 255)   // before the matrix is looked at
+        return fail(SM_ERR_INVALID_ARG, "table_size %d not in [1, 255]", table_size);
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (m->nnz == 0) return SM_OK;
+    if (!d_table || !d_ids) return fail(SM_ERR_INVALID_ARG, "sm_quantize_assign: null array");
+    DeviceGuard g(m->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = launch_quantize_assign(m->nnz, m->d_val, d_table, table_size, d_ids, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e == hipSuccess ? SM_OK : hip_fail(e, "sm_quantize_assign");
+}
+
+sm_status sm_quantize_update(const sm_matrix *m, const uint8_t *d_ids, int32_t table_size, float *d_table,
+                             int32_t *d_counts, double *d_sse, sm_stream stream) {
+    if (table_size < 1 || table_size > 255)   // before the matrix is looked at
+        return fail(SM_ERR_INVALID_ARG, "table_size %d not in [1, 255]", table_size);
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (!d_table || (m->nnz > 0 && !d_ids)) return fail(SM_ERR_INVALID_ARG, "sm_quantize_update: null array");
+    DeviceGuard g(m->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t chunks = (m->nnz + kSddmmChunk - 1) / kSddmmChunk;
+    DevScratch tmp;
+    double *d_psum = nullptr;
+    int32_t *d_pcnt = nullptr, *d_flag = nullptr;
+    int32_t flag = 0;
+    hipError_t e = tmp.alloc(&d_psum, chunks * kTablePartialStride);
+    if (e == hipSuccess) e = tmp.alloc(&d_pcnt, chunks * kTablePartialStride);
+    if (e == hipSuccess) e = tmp.alloc(&d_flag, 1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), s);
+    if (e == hipSuccess)
+        e = launch_quantize_chunks(m->nnz, m->d_val, d_table, table_size, d_ids, d_psum, d_pcnt, d_flag, s);
+    if (e == hipSuccess) e = launch_quantize_finish(chunks, table_size, d_psum, d_pcnt, d_table, d_counts, d_sse, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return hip_fail(e, "sm_quantize_update");
+    }
+    if (flag) return fail(SM_ERR_INVALID_MATRIX, "sm_quantize_update: an id is >= table_size %d", table_size);
+    return SM_OK;
+}
+
+sm_status sm_create_quantized(const sm_matrix *src, int32_t table_size, int32_t iters, const float *d_init,
+                              const sm_build_opts *opts, sm_stream stream, sm_matrix **out) {
+    if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (table_size < 1 || table_size > 255)   // before the matrix is looked at
+        return fail(SM_ERR_INVALID_ARG, "table_size %d not in [1, 255]", table_size);
+    if (iters < 0) return fail(SM_ERR_INVALID_ARG, "iters %d < 0", iters);
+    sm_status st = check_table_opts(opts);
+    if (st != SM_OK) return st;
+    if (!src) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    DeviceGuard g(src->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nnz = src->nnz;
+    const int32_t T = table_size;
+    const int64_t chunks = (nnz + kSddmmChunk - 1) / kSddmmChunk, parts = quantize_minmax_blocks(nnz);
+    DevScratch tmp;
+    float *d_table = nullptr, *d_parts = nullptr;
+    uint8_t *d_ids = nullptr;
+    double *d_psum = nullptr;
+    int32_t *d_pcnt = nullptr, *d_flag = nullptr;
+    int32_t flag = 0;
+    std::vector<float> h_parts((size_t)parts * 2), h_table((size_t)T);
+    hipError_t e = tmp.alloc(&d_table, T);
+    if (e == hipSuccess) e = tmp.alloc(&d_ids, nnz);
+    if (e == hipSuccess) e = tmp.alloc(&d_parts, parts * 2);
+    if (e == hipSuccess) e = tmp.alloc(&d_flag, 2);
+    if (e == hipSuccess && iters > 0) e = tmp.alloc(&d_psum, chunks * kTablePartialStride);
+    if (e == hipSuccess && iters > 0) e = tmp.alloc(&d_pcnt, chunks * kTablePartialStride);
+    // The least and greatest value (the linear start) and the finiteness check, which runs also
+    // when the start is given.
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 2 * sizeof(int32_t), s);
+    if (e == hipSuccess) e = launch_quantize_minmax(nnz, src->d_val, d_parts, d_flag, s);
+    if (e == hipSuccess && parts)
+        e = hipMemcpyAsync(h_parts.data(), d_parts, h_parts.size() * sizeof(float), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return hip_fail(e, "sm_create_quantized (value range)");
+    }
+    if (flag) return fail(SM_ERR_INVALID_MATRIX, "sm_create_quantized: a stored value is NaN or Inf");
+    if (d_init) {
+        e = hipMemcpyAsync(d_table, d_init, (size_t)T * sizeof(float), hipMemcpyDeviceToDevice, s);
+    } else {
+        float lo = 0.0f, hi = 0.0f;   // no term: all zeros
+        for (int64_t b = 0; b < parts; b++) {
+            lo = b ? std::min(lo, h_parts[(size_t)(2 * b)]) : h_parts[0];
+            hi = b ? std::max(hi, h_parts[(size_t)(2 * b + 1)]) : h_parts[1];
+        }
+        const double dlo = (double)lo + 0.0, dhi = (double)hi + 0.0;   // a zero bound counts as +0.0
+        for (int32_t t = 0; t < T; t++)
+            h_table[(size_t)t] = T == 1 ? (float)((dlo + dhi) / 2) : (float)(dlo + (dhi - dlo) * ((double)t / (double)(T - 1)));
+        e = hipMemcpyAsync(d_table, h_table.data(), (size_t)T * sizeof(float), hipMemcpyHostToDevice, s);
+    }
+    // Lloyd: the launches of sm_quantize_assign and sm_quantize_update, with no synchronise or
+    // allocation between them; the last assignment makes the ids those of the final table.
+    for (int32_t it = 0; it < iters && e == hipSuccess; it++) {
+        e = launch_quantize_assign(nnz, src->d_val, d_table, T, d_ids, s);
+        if (e == hipSuccess) e = launch_quantize_chunks(nnz, src->d_val, d_table, T, d_ids, d_psum, d_pcnt, d_flag + 1, s);
+        if (e == hipSuccess) e = launch_quantize_finish(chunks, T, d_psum, d_pcnt, d_table, nullptr, nullptr, s);
+    }
+    if (e == hipSuccess) e = launch_quantize_assign(nnz, src->d_val, d_table, T, d_ids, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // h_table is read until here
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return hip_fail(e, "sm_create_quantized");
+    }
+    return create_from_ids_device(src->n_rows, src->n_cols, nnz, src->d_row_ptr, src->d_col, d_ids, d_table, T,
+                                  src->device, s, opts, out);
+}
+
 sm_status sm_get_info(const sm_matrix *m, sm_info *info) {
     return sm_get_info_ex(m, info, sizeof(sm_info));
 }

@@ -475,6 +475,25 @@ struct TableDst {
 hipError_t launch_table_step(int32_t table_size, bool axpy, float a, const float *in, float *tab,
                              const TableDst &dst, hipStream_t s);
 hipError_t launch_values_from_table(int64_t nnz, const uint8_t *ids, const float *tab, float *val, hipStream_t s);
+// Quantising the stored values (kernels_quantize.hip).  launch_expand_ids: val[e] = table[ids[e]]
+// bit for bit (`table`: T floats on the device; any alignment of `ids`), *flag |= 1 on an id >= T.
+// launch_quantize_minmax: parts[2b], parts[2b + 1] = the least / greatest value of workgroup b's
+// share (quantize_minmax_blocks(nnz) workgroups), *flag |= 1 on a NaN or Inf.
+// launch_quantize_assign: sm_quantize_assign's rule for every term.  launch_quantize_chunks: the
+// per-chunk sums, counts and squared distances of sm_quantize_update into psum / pcnt
+// (ceil(nnz / kSddmmChunk) rows of kTablePartialStride; the sse in slot 255), *flag |= 1 on an id
+// >= T.  launch_quantize_finish: the chunks in ascending order, the new table, counts and sse
+// (either may be null).
+hipError_t launch_expand_ids(int64_t nnz, const uint8_t *ids, const float *table, int32_t T, float *val,
+                             int32_t *flag, hipStream_t s);
+int64_t quantize_minmax_blocks(int64_t nnz);
+hipError_t launch_quantize_minmax(int64_t nnz, const float *val, float *parts, int32_t *flag, hipStream_t s);
+hipError_t launch_quantize_assign(int64_t nnz, const float *val, const float *table, int32_t T, uint8_t *ids,
+                                  hipStream_t s);
+hipError_t launch_quantize_chunks(int64_t nnz, const float *val, const float *table, int32_t T, const uint8_t *ids,
+                                  double *psum, int32_t *pcnt, int32_t *flag, hipStream_t s);
+hipError_t launch_quantize_finish(int64_t n_chunks, int32_t T, const double *psum, const int32_t *pcnt, float *table,
+                                  int32_t *counts, double *sse, hipStream_t s);
 hipError_t launch_validate(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t *rp,
                            const int32_t *col, int32_t *d_flag, hipStream_t s);
 // Dense decode: out is zeroed by the caller.  b_layout: out[row*stride+col]

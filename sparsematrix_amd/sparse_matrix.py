@@ -218,7 +218,10 @@ class SparseMatrix:
         Host (numpy) arrays; `ids`: nnz uint8 in CSR order, each < T.  Without options the matrix
         is what from_csr builds from ``table[ids]``; it also remembers ids and table, so
         sddmm_table applies.  ``opts={"table_updatable": 1}`` builds every layout in its codebook
-        form from the given ids and table, so set_table / axpy_table replace the table in place."""
+        form from the given ids and table, so set_table / axpy_table replace the table in place.
+        Torch device tensors (all four) go to from_csr_ids_device on the current torch stream."""
+        if any(_is_device(a) for a in (row_ptr, col_idx, ids, table)):
+            return cls.from_csr_ids_device(row_ptr, col_idx, ids, table, n_cols, device=device, opts=opts)
         self = cls(device=device)
         rp = np.ascontiguousarray(row_ptr, np.int32)
         ci = np.ascontiguousarray(col_idx, np.int32)
@@ -233,6 +236,41 @@ class SparseMatrix:
         st = self._L.sm_create_from_csr_ids(int(rp.shape[0]) - 1, n_cols, int(ci.size), _ptr(rp), _ptr(ci),
                                             _ptr(idv), _ptr(tb), int(tb.size), device, C.byref(o), C.byref(h))
         check(st, "from_csr_ids")
+        self._h = h
+        return self
+
+    @classmethod
+    def from_csr_ids_device(cls, row_ptr, col_idx, ids, table, n_cols: int, device: int = 0,
+                            opts: Optional[dict] = None, stream=None) -> "SparseMatrix":
+        """from_csr_ids from torch tensors on `device` (sm_create_from_csr_ids_device): int32
+        `row_ptr` / `col_idx`, uint8 `ids` (nnz, each < T), float32 `table` (T <= 255).  The result
+        is the matrix from_csr_ids builds from the same arrays on the host, bit for bit; no array
+        goes to the host unless ``opts={"table_updatable": 1}`` (then the ids and the table do,
+        once).  Synchronises `stream` (None: the current torch stream)."""
+        import torch
+        for a, dt, name in ((row_ptr, torch.int32, "row_ptr"), (col_idx, torch.int32, "col_idx"),
+                            (ids, torch.uint8, "ids"), (table, torch.float32, "table")):
+            if not isinstance(a, torch.Tensor) or not a.is_cuda:
+                raise TypeError(f"{name} must be a CUDA (HIP) torch tensor")
+            if a.dtype != dt:
+                raise TypeError(f"{name} must be {dt}")
+            if a.device.index != device:
+                raise ValueError(f"{name} must be on device {device}")
+        rp, ci = row_ptr.contiguous().reshape(-1), col_idx.contiguous().reshape(-1)
+        idv, tb = ids.contiguous().reshape(-1), table.contiguous().reshape(-1)
+        if rp.numel() < 1:
+            raise ValueError("row_ptr needs n_rows + 1 elements")
+        if idv.numel() != ci.numel():
+            raise ValueError(f"ids has {idv.numel()} elements, col_idx {ci.numel()}")
+        if tb.numel() > 255 or (ci.numel() > 0 and tb.numel() < 1):
+            raise ValueError(f"table must hold 1..255 values, got {tb.numel()}")
+        self = cls(device=device)
+        h = C.c_void_p()
+        o = _lib.build_opts(**(opts or {}))
+        st = self._L.sm_create_from_csr_ids_device(int(rp.numel()) - 1, n_cols, int(ci.numel()), _ptr(rp), _ptr(ci),
+                                                   _ptr(idv), _ptr(tb), int(tb.numel()), device,
+                                                   _stream_of(rp, stream), C.byref(o), C.byref(h))
+        check(st, "from_csr_ids_device")
         self._h = h
         return self
 
@@ -624,6 +662,76 @@ class SparseMatrix:
         check(self._L.sm_axpy_table(h, a, _ptr(delta), s), "sm_axpy_table")
         if self._t is not None:
             check(self._L.sm_axpy_table(self._t._require(), a, _ptr(delta), s), "sm_axpy_table (T)")
+
+    # ---- quantising the stored values: k-means on the device ---------------------------------
+    def _codebook_operand(self, t, name: str) -> int:
+        """T of a table operand of the quantiser: 1..255 float32 elements on the matrix's device."""
+        _check_dev(t, 1, name)
+        if t.dim() != 1 or t.numel() > 255 or (t.numel() > 1 and t.stride(0) != 1):
+            raise ValueError(f"{name} must be a unit-stride 1-D tensor of 1..255 elements")
+        if t.device.index != self.device:
+            raise ValueError(f"{name} must be on the matrix's device")
+        return int(t.numel())
+
+    def quantize_assign(self, table, stream=None):
+        """ids[e] = the entry of `table` nearest to the stored value of term e (sm_quantize_assign;
+        the header states the tie rule), for the stored values of any matrix: a new uint8 tensor of
+        nnz elements on the matrix's device.  `table`: 1..255 float32 elements on that device.
+        Synchronises `stream` (None: the current torch stream)."""
+        import torch
+        h = self._require()
+        T = self._codebook_operand(table, "table")
+        ids = torch.empty(self._nnz(), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        st = self._L.sm_quantize_assign(h, _ptr(table), T, _ptr(ids) if ids.numel() else 0,
+                                        _stream_of(ids, stream))
+        check(st, "sm_quantize_assign")
+        return ids
+
+    def quantize_update(self, ids, table, stream=None):
+        """One Lloyd update (sm_quantize_update): table[t] <- the mean of the stored values with id
+        t, in place (an id with no value keeps its entry), summed in double in the header's fixed
+        order.  `ids`: nnz uint8 elements, `table`: 1..255 float32 elements, both on the matrix's
+        device.  Returns (counts, sse): an int32 tensor of T elements and the sum of squared
+        distances to the OLD table as a float64 tensor of one element.  Synchronises `stream`."""
+        import torch
+        h = self._require()
+        T = self._codebook_operand(table, "table")
+        nnz = self._nnz()
+        if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.dtype != torch.uint8:
+            raise TypeError("ids must be a CUDA (HIP) uint8 torch tensor")
+        if ids.dim() != 1 or ids.numel() != nnz or (nnz > 1 and ids.stride(0) != 1):
+            raise ValueError(f"ids must be a unit-stride 1-D tensor of nnz = {nnz} elements")
+        if ids.device.index != self.device:
+            raise ValueError("ids must be on the matrix's device")
+        dev = torch.device("cuda", self.device)
+        counts = torch.empty(T, dtype=torch.int32, device=dev)
+        sse = torch.empty(1, dtype=torch.float64, device=dev)
+        st = self._L.sm_quantize_update(h, _ptr(ids) if nnz else 0, T, _ptr(table), _ptr(counts), _ptr(sse),
+                                        _stream_of(table, stream))
+        check(st, "sm_quantize_update")
+        return counts, sse
+
+    def quantized(self, table_size: int = 255, iters: int = 8, init=None, opts: Optional[dict] = None,
+                  stream=None) -> "SparseMatrix":
+        """A new table matrix with this matrix's pattern and its stored values quantised to
+        `table_size` <= 255 shared values by `iters` k-means (Lloyd) steps on the device
+        (sm_create_quantized): the start is `init` (table_size float32 elements on the matrix's
+        device) or, for None, the linear table between the least and greatest value.  This matrix
+        is only read.  `opts`: as for from_csr_ids -- ``{"table_updatable": 1}`` for fine-tuning the
+        table with sddmm_table / axpy_table.  A NaN or Inf value raises (invalid matrix).
+        Synchronises `stream` (None: the current torch stream)."""
+        h0 = self._require()
+        table_size, iters = int(table_size), int(iters)
+        if init is not None and self._codebook_operand(init, "init") != table_size:
+            raise ValueError(f"init must hold table_size = {table_size} elements")
+        q = SparseMatrix(device=self.device)
+        o = _lib.build_opts(**(opts or {}))
+        h = C.c_void_p()
+        st = self._L.sm_create_quantized(h0, table_size, iters, _ptr(init), C.byref(o), _stream_of(self, stream),
+                                         C.byref(h))
+        check(st, "quantized")
+        q._h = h
+        return q
 
     def csr_device(self, stream=None):
         """(row_ptr, col_idx, val): new torch tensors on the matrix's device holding its CSR
