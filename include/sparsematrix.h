@@ -498,6 +498,79 @@ SM_API sm_status sm_create_quantized(const sm_matrix *src, int32_t table_size, i
 SM_API sm_status sm_copy_table_device(const sm_matrix *m, float *d_table, sm_stream stream);
 SM_API sm_status sm_copy_term_ids_device(const sm_matrix *m, uint8_t *d_ids, sm_stream stream);
 
+/* ---- pruning the stored terms by magnitude: mask, compact, rebuild ------------------------------
+ * The "prune" step of prune -> quantise -> fine-tune: from the stored fp32 values of any matrix
+ * (m->d_val in CSR order, whatever constructor made it) to a mask of the terms to keep, and from a
+ * mask to a new matrix that holds the kept terms and remembers where each came from.  The source
+ * is only read.  The calls allocate their own scratch and synchronise `stream`: they are not meant
+ * for graph capture.
+ *
+ * The selection rule (sm_prune_mask), on integers only, so that it can be restated bit for bit:
+ *   Key.  key(v) = bits(v) & 0x7FFFFFFF, compared as an unsigned integer: -0.0 and +0.0 tie,
+ *     subnormals order as their magnitudes, Inf beats every finite value and a NaN has the greatest
+ *     keys of all -- it is kept first; the library never drops a NaN weight silently.  Unlike
+ *     sm_create_quantized, no stored value is an error here.
+ *   SM_PRUNE_GLOBAL_TOPK.  The terms ordered by (key descending, CSR index ascending); the first
+ *     min(count, nnz) are kept.  Ties at the cut go to the lower CSR index.
+ *   SM_PRUNE_ROW_TOPK.  The same order within every row (ties to the earlier stored position);
+ *     the first min(count, row length) of each row are kept.
+ *   SM_PRUNE_THRESHOLD.  Term e is kept iff key(val[e]) >= key(threshold).  `count` is ignored.
+ *     threshold = 0 keeps every term, explicit zeros included; -0.0 counts as 0.
+ * Argument errors, all SM_ERR_INVALID_ARG and checked before the matrix is looked at: an unknown
+ *   mode; count < 0 in the two top-k modes; a NaN or negative threshold (but -0.0) in
+ *   SM_PRUNE_THRESHOLD (`threshold` is ignored in the other modes); a null `out`.  Then a null
+ *   matrix, and a null d_keep with nnz > 0.  count = 0 is legal: an all-zero mask, an empty matrix.
+ * d_keep: nnz bytes on the matrix's device at any alignment, keep[e] = 1 or 0; nothing outside
+ *   keep[0, nnz) is written.  *kept (host, may be NULL) = the number of ones.  nnz == 0 launches
+ *   nothing.
+ * Deterministic: the mask is a function of the stored values (and row_ptr) alone.  The kernels use
+ *   integer atomics on counters (counts are exact and their order reaches nothing) and no float
+ *   arithmetic at all; every launch geometry is a function of nnz and n_rows alone.
+ * Scratch: GLOBAL_TOPK 8 bytes per 2048 terms + 4 KiB + hipCUB's scan storage; ROW_TOPK 4 bytes
+ *   per row + at most 16 KiB; THRESHOLD at most 8 KiB.
+ *
+ * sm_create_masked: a new, independent matrix holding the terms of src whose keep[e] != 0, in
+ * stored order (d_keep: nnz bytes on src's device, any alignment; NULL only with nnz == 0).  One
+ * exclusive scan of the mask over nnz + 1 positions gives every kept term's new index, the new
+ * nnz and the new row pointer (new_rp[r] = pos[old_rp[r]]); one kernel scatters the columns, the
+ * values (a bit copy) and the source map; then the tail of the device constructors runs, so the
+ * layouts, and where the device builders run, are exactly those of sm_create_from_csr_device_ex
+ * (a table source: sm_create_from_csr_ids_device) on the compacted arrays with the same `opts`
+ * (NULL: defaults): sm_equal, sm_layout_digest, sm_info (device_bytes aside), sm_built_on_device
+ * and every product of every sm_algo, bit for bit.  Rows with unsorted or repeated columns pass
+ * through in stored order; the layouts that need ascending columns decline them as ever.
+ *   A table source (sm_create_from_csr_ids and its kin) gives a table matrix: the ids go through
+ *   the same scatter, the table is the source's current one (all table_size entries, also those no
+ *   kept term uses), opts->table_updatable is honoured (the ids and the table are copied to the
+ *   host once for the host builders) -- as sm_create_transpose hands a table matrix on.
+ *   A dense-index (CopyForm) source gives an ordinary CSR matrix of its values: neither the
+ *   codebook nor the reference stream is handed on (sm_info.table_size and has_ref_stream are 0).
+ *   The source map -- per kept term its CSR index in src, int32, counted in sm_info.device_bytes
+ *   -- is always kept: sm_copy_source_terms_device reads it, and with opts->updatable = 1 the
+ *   result takes sm_set_values / sm_axpy_values in SM_VALUES_SOURCE order, so values, gradients
+ *   and optimiser state laid out for the unpruned matrix can be used as they are.
+ * Scratch while building: 4 bytes per term of src + hipCUB's scan storage.
+ *
+ * sm_create_pruned: sm_prune_mask, then sm_create_masked, the mask (1 more byte per term of
+ * scratch) never being the caller's.
+ *
+ * sm_copy_source_terms_device: for a matrix made by sm_create_masked / sm_create_pruned, and by
+ * sm_create_transpose with opts->updatable = 1 (which holds the same map): terms[e] = the CSR
+ * index in the source of the matrix's term e.  nnz int32 on the matrix's device, asynchronous on
+ * `stream`.  SM_ERR_NOT_SUPPORTED on a matrix that holds no such map. */
+typedef enum sm_prune_mode {
+    SM_PRUNE_GLOBAL_TOPK = 0,  /* keep the `count` terms of greatest |value| of the whole matrix   */
+    SM_PRUNE_ROW_TOPK    = 1,  /* keep, in every row, its `count` terms of greatest |value|         */
+    SM_PRUNE_THRESHOLD   = 2   /* keep the terms whose |value| is not below `threshold`             */
+} sm_prune_mode;
+SM_API sm_status sm_prune_mask(const sm_matrix *m, sm_prune_mode mode, int64_t count, float threshold,
+                               uint8_t *d_keep, int64_t *kept /* host, may be NULL */, sm_stream stream);
+SM_API sm_status sm_create_masked(const sm_matrix *src, const uint8_t *d_keep, const sm_build_opts *opts,
+                                  sm_stream stream, sm_matrix **out);
+SM_API sm_status sm_create_pruned(const sm_matrix *src, sm_prune_mode mode, int64_t count, float threshold,
+                                  const sm_build_opts *opts, sm_stream stream, sm_matrix **out);
+SM_API sm_status sm_copy_source_terms_device(const sm_matrix *m, int32_t *d_terms, sm_stream stream);
+
 /* Destroy: sparse-matrix.cc:9-18 (frees host and device storage). */
 SM_API void sm_destroy(sm_matrix *m);
 
@@ -631,8 +704,9 @@ SM_API sm_status sm_sddmm(const sm_matrix *m, int32_t n_rhs, float alpha, const 
  *   sm_axpy_values:  val[e] = fl(val[e] + fl(a * delta[i])) -- two roundings, no fused multiply-add.
  * `order` says how the array is indexed.  SM_VALUES_OWN: i = e, the matrix's own CSR order (the
  * order of sm_copy_csr and of sm_sddmm's `out`).  SM_VALUES_SOURCE: the array is in the CSR order
- * of the matrix this one was transposed from -- term e reads the element of its source term; only
- * on a matrix sm_create_transpose made with opts->updatable = 1 (SM_ERR_NOT_SUPPORTED otherwise).
+ * of the matrix this one was made from -- transposed (sm_create_transpose) or pruned
+ * (sm_create_masked / sm_create_pruned) -- and term e reads the element of its source term; only
+ * on a matrix one of those calls made with opts->updatable = 1 (SM_ERR_NOT_SUPPORTED otherwise).
  * Both orders apply the same roundings to the same operands: after the same call on a matrix
  * and on its transposed companion the two hold the same bits per term.
  * Afterwards the matrix is what sm_create_from_csr_device_ex builds from (row_ptr, col_idx, the

@@ -29,9 +29,10 @@ SM_ERR_TOO_LARGE = 5
 SM_ERR_INVALID_MATRIX = 6
 SM_ERR_NO_DEVICE = 7
 
-# sm_trans / sm_algo / sm_values_order
+# sm_trans / sm_algo / sm_values_order / sm_prune_mode
 SM_NO_TRANS, SM_TRANS = 0, 1
 SM_VALUES_OWN, SM_VALUES_SOURCE = 0, 1
+SM_PRUNE_GLOBAL_TOPK, SM_PRUNE_ROW_TOPK, SM_PRUNE_THRESHOLD = 0, 1, 2
 ALGOS = {"auto": 0, "parity": 1, "stream": 2, "vector": 3, "xband": 4, "sell": 5, "native": 6,
          "exact": 7, "mfma": 8, "merge": 9}
 
@@ -53,6 +54,7 @@ EXPORTS = (
     "sm_create_from_csr_ids", "sm_copy_table_device", "sm_copy_term_ids_device", "sm_sddmm_table",
     "sm_set_table", "sm_axpy_table",
     "sm_create_from_csr_ids_device", "sm_quantize_assign", "sm_quantize_update", "sm_create_quantized",
+    "sm_prune_mask", "sm_create_masked", "sm_create_pruned", "sm_copy_source_terms_device",
 )
 
 SM_UNIQUE_ID_BYTES = 128
@@ -173,6 +175,10 @@ def _declare(L):
         "sm_quantize_assign": ([_vp, _vp, _i32, _vp, _vp], C.c_int),
         "sm_quantize_update": ([_vp, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
         "sm_create_quantized": ([_vp, _i32, _i32, _vp, C.POINTER(SmBuildOpts), _vp, C.POINTER(_vp)], C.c_int),
+        "sm_prune_mask": ([_vp, C.c_int, _i64, _f32, _vp, C.POINTER(_i64), _vp], C.c_int),
+        "sm_create_masked": ([_vp, _vp, C.POINTER(SmBuildOpts), _vp, C.POINTER(_vp)], C.c_int),
+        "sm_create_pruned": ([_vp, C.c_int, _i64, _f32, C.POINTER(SmBuildOpts), _vp, C.POINTER(_vp)], C.c_int),
+        "sm_copy_source_terms_device": ([_vp, _vp, _vp], C.c_int),
         "sm_copy_table_device": ([_vp, _vp, _vp], C.c_int),
         "sm_copy_term_ids_device": ([_vp, _vp, _vp], C.c_int),
         "sm_sddmm_table": ([_vp, _i32, _f32, _vp, _i64, _vp, _i64, _f32, _vp, C.c_int, _vp], C.c_int),

@@ -822,6 +822,134 @@ sm_status sm_create_quantized(const sm_matrix *src, int32_t table_size, int32_t 
                                   src->device, s, opts, out);
 }
 
+// What sm_prune_mask and sm_create_pruned check before the matrix is looked at.
+static sm_status check_prune_args(sm_prune_mode mode, int64_t count, float threshold) {
+    if (mode != SM_PRUNE_GLOBAL_TOPK && mode != SM_PRUNE_ROW_TOPK && mode != SM_PRUNE_THRESHOLD)
+        return fail(SM_ERR_INVALID_ARG, "unknown sm_prune_mode %d", (int)mode);
+    if (mode != SM_PRUNE_THRESHOLD && count < 0) return fail(SM_ERR_INVALID_ARG, "count %lld < 0", (long long)count);
+    if (mode == SM_PRUNE_THRESHOLD && !(threshold >= 0.0f))   // NaN compares false; -0.0 >= 0 holds
+        return fail(SM_ERR_INVALID_ARG, "threshold must be a number >= 0");
+    return SM_OK;
+}
+
+sm_status sm_prune_mask(const sm_matrix *m, sm_prune_mode mode, int64_t count, float threshold, uint8_t *d_keep,
+                        int64_t *kept, sm_stream stream) {
+    if (const sm_status st = check_prune_args(mode, count, threshold)) return st;
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (kept) *kept = 0;
+    if (m->nnz == 0) return SM_OK;
+    if (!d_keep) return fail(SM_ERR_INVALID_ARG, "sm_prune_mask: null array");
+    DeviceGuard g(m->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    const hipError_t e = prune_mask_device(m->d_row_ptr, m->d_val, m->n_rows, m->nnz, mode, count, threshold, d_keep,
+                                           kept, (hipStream_t)stream);
+    return e == hipSuccess ? SM_OK : hip_fail(e, "sm_prune_mask");
+}
+
+// The compaction of `src` by a mask on its device, the arguments checked and the device current:
+// positions, the new matrix's arrays filled by one scatter, a table source's ids and table handed
+// on as sm_create_transpose does, then the device-CSR constructors' tail.
+static sm_status create_masked(const sm_matrix *src, const uint8_t *d_keep, const sm_build_opts *opts, hipStream_t s,
+                               sm_matrix **out) {
+    DevScratch tmp;
+    int32_t *d_pos = nullptr;
+    int64_t new_nnz = 0;
+    hipError_t e = tmp.alloc(&d_pos, src->nnz + 1);
+    if (e == hipSuccess) e = prune_positions_device(src->nnz, d_keep, d_pos, &new_nnz, s);
+    if (e != hipSuccess) return hip_fail(e, "sm_create_masked (positions)");
+    auto m = new_matrix(src->device, opts);
+    set_shape(m.get(), src->n_rows, src->n_cols, new_nnz);
+    sm_status st = alloc_csr(m.get());
+    m->has_src_term = true;
+    if (st == SM_OK && new_nnz > 0) {
+        e = m->mem.alloc(&m->d_src_term, new_nnz);
+        if (e != hipSuccess) st = hip_fail(e, "sm_create_masked (source terms)");
+    }
+    if (st == SM_OK && src->is_table) {
+        st = alloc_table(m.get(), nullptr, src->tab_size);
+        if (st == SM_OK) {
+            e = hipStreamSynchronize(nullptr);   // alloc_table zeroed the table on the default stream
+            if (e == hipSuccess) e = hipMemcpyAsync(m->d_tab, src->d_tab, 256 * sizeof(float), hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) st = hip_fail(e, "sm_create_masked (table)");
+        }
+    }
+    if (st == SM_OK) {
+        e = launch_prune_compact(src->n_rows, src->nnz, d_keep, d_pos, src->d_row_ptr, src->d_col, src->d_val,
+                                 src->is_table ? src->d_tab_ids : nullptr, m->d_row_ptr, m->d_col, m->d_val,
+                                 m->d_src_term, m->d_tab_ids, new_nnz > 0, s);
+        if (e != hipSuccess) st = hip_fail(e, "sm_create_masked (scatter)");
+    }
+    std::vector<uint8_t> h_ids;
+    std::vector<float> h_tab;
+    if (st == SM_OK && src->is_table && m->opts.table_updatable) {   // 1 byte per term and the table come down once
+        h_ids.resize((size_t)new_nnz);
+        h_tab.resize(256);
+        e = hipStreamSynchronize(s);
+        if (e == hipSuccess && new_nnz > 0) e = hipMemcpy(h_ids.data(), m->d_tab_ids, (size_t)new_nnz, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(h_tab.data(), m->d_tab, 256 * sizeof(float), hipMemcpyDeviceToHost);
+        m->build_ids = h_ids.data();
+        m->build_table = h_tab.data();
+        if (e != hipSuccess) st = hip_fail(e, "sm_create_masked (table)");
+    }
+    if (st == SM_OK) st = finish_from_device_csr(m.get(), s, src->is_table);   // synchronises s: d_pos is free to go
+    m->build_ids = nullptr;
+    m->build_table = nullptr;
+    if (st != SM_OK) {
+        (void)hipStreamSynchronize(s);
+        m.reset();
+        (void)hipGetLastError();   // a failed allocation leaves no sticky error behind
+        return st;
+    }
+    *out = m.release();
+    return SM_OK;
+}
+
+sm_status sm_create_masked(const sm_matrix *src, const uint8_t *d_keep, const sm_build_opts *opts, sm_stream stream,
+                           sm_matrix **out) {
+    if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (!src) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (const sm_status st = check_opts(opts, src->is_table)) return st;
+    if (src->nnz > 0 && !d_keep) return fail(SM_ERR_INVALID_ARG, "sm_create_masked: null array");
+    DeviceGuard g(src->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    return create_masked(src, d_keep, opts, (hipStream_t)stream, out);
+}
+
+sm_status sm_create_pruned(const sm_matrix *src, sm_prune_mode mode, int64_t count, float threshold,
+                           const sm_build_opts *opts, sm_stream stream, sm_matrix **out) {
+    if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (const sm_status st = check_prune_args(mode, count, threshold)) return st;
+    if (!src) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (const sm_status st = check_opts(opts, src->is_table)) return st;
+    DeviceGuard g(src->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    DevScratch tmp;
+    uint8_t *d_keep = nullptr;
+    hipError_t e = tmp.alloc(&d_keep, src->nnz);
+    if (e == hipSuccess)
+        e = prune_mask_device(src->d_row_ptr, src->d_val, src->n_rows, src->nnz, mode, count, threshold, d_keep, nullptr, s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return hip_fail(e, "sm_create_pruned (mask)");
+    }
+    return create_masked(src, d_keep, opts, s, out);
+}
+
+sm_status sm_copy_source_terms_device(const sm_matrix *m, int32_t *d_terms, sm_stream stream) {
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (!m->has_src_term)
+        return fail(SM_ERR_NOT_SUPPORTED, "sm_copy_source_terms_device: the matrix holds no source map (sm_create_masked, "
+                                          "sm_create_pruned, or sm_create_transpose with updatable)");
+    if (m->nnz == 0) return SM_OK;
+    if (!d_terms) return fail(SM_ERR_INVALID_ARG, "sm_copy_source_terms_device: null array");
+    DeviceGuard g(m->device);
+    SM_TRY_HIP(hipMemcpyAsync(d_terms, m->d_src_term, (size_t)m->nnz * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SM_OK;
+}
+
 sm_status sm_get_info(const sm_matrix *m, sm_info *info) {
     return sm_get_info_ex(m, info, sizeof(sm_info));
 }
@@ -1323,7 +1451,9 @@ static sm_status update_values(sm_matrix *m, bool axpy, float a, const float *d_
     if (!m->opts.updatable)
         return fail(SM_ERR_NOT_SUPPORTED, "%s: the matrix was not built with sm_build_opts.updatable", what);
     if (order == SM_VALUES_SOURCE && !m->has_src_term)
-        return fail(SM_ERR_NOT_SUPPORTED, "%s: SM_VALUES_SOURCE needs a matrix made by sm_create_transpose", what);
+        return fail(SM_ERR_NOT_SUPPORTED,
+                    "%s: SM_VALUES_SOURCE needs a matrix made by sm_create_transpose, sm_create_masked or sm_create_pruned",
+                    what);
     if (m->nnz == 0 || (axpy && a == 0.0f)) return SM_OK;
     if (!d_in) return fail(SM_ERR_INVALID_ARG, "%s: null array", what);
     DeviceGuard g(m->device);

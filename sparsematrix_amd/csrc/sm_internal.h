@@ -494,6 +494,21 @@ hipError_t launch_quantize_chunks(int64_t nnz, const float *val, const float *ta
                                   double *psum, int32_t *pcnt, int32_t *flag, hipStream_t s);
 hipError_t launch_quantize_finish(int64_t n_chunks, int32_t T, const double *psum, const int32_t *pcnt, float *table,
                                   int32_t *counts, double *sse, hipStream_t s);
+// Pruning the stored terms (kernels_prune.hip).  prune_mask_device: sm_prune_mask's rule for the
+// values of a validated device CSR into keep[0, nnz) (any alignment), *kept (host, may be null)
+// the number of ones; the arguments are checked by the caller; allocates its scratch, synchronises
+// `s` and leaves no sticky HIP error on failure.  prune_positions_device: pos[e] = the number of
+// kept terms before e, for e in [0, nnz] (`pos`: nnz + 1 entries), *new_nnz = pos[nnz];
+// synchronises `s`.  launch_prune_compact: new_rp[r] = pos[rp[r]] and, for every kept term e,
+// new_col / new_val / src_term (/ new_ids when `ids` is given) at pos[e]; `any_kept` false: only
+// the row pointer (the term arrays may then be null).
+hipError_t prune_mask_device(const int32_t *rp, const float *val, int64_t n_rows, int64_t nnz, sm_prune_mode mode,
+                             int64_t count, float threshold, uint8_t *keep, int64_t *kept, hipStream_t s);
+hipError_t prune_positions_device(int64_t nnz, const uint8_t *keep, int32_t *pos, int64_t *new_nnz, hipStream_t s);
+hipError_t launch_prune_compact(int64_t n_rows, int64_t nnz, const uint8_t *keep, const int32_t *pos,
+                                const int32_t *rp, const int32_t *col, const float *val, const uint8_t *ids,
+                                int32_t *new_rp, int32_t *new_col, float *new_val, int32_t *src_term, uint8_t *new_ids,
+                                bool any_kept, hipStream_t s);
 hipError_t launch_validate(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t *rp,
                            const int32_t *col, int32_t *d_flag, hipStream_t s);
 // Dense decode: out is zeroed by the caller.  b_layout: out[row*stride+col]
@@ -536,8 +551,9 @@ struct sm_matrix {
     // they index `table` and exist only while has_ref is false (sm_build_ref_stream frees them:
     // the stream then holds the ids, and sm_create_transpose reads them back from it).
     uint8_t *d_term_ids = nullptr;
-    // Updatable matrix made by sm_create_transpose: per term its CSR index in the source matrix
-    // (nnz entries), so values given in the source's order reach it (SM_VALUES_SOURCE).
+    // Updatable matrix made by sm_create_transpose, and every matrix made by sm_create_masked /
+    // sm_create_pruned: per term its CSR index in the source matrix (nnz entries), so values given
+    // in the source's order reach it (SM_VALUES_SOURCE; sm_copy_source_terms_device reads it).
     int32_t *d_src_term = nullptr;
     bool has_src_term = false;   // (also true with nnz == 0, where there is nothing to allocate)
     // Table matrix (sm_create_from_csr_ids and its transposes): the terms' ids (nnz bytes, CSR

@@ -733,6 +733,85 @@ class SparseMatrix:
         q._h = h
         return q
 
+    # ---- pruning the stored terms by magnitude: mask, compact, rebuild ------------------------
+    @staticmethod
+    def _prune_args(keep, per_row, threshold):
+        """(mode, count, threshold) of the C ABI from the three exclusive keyword arguments."""
+        if sum(a is not None for a in (keep, per_row, threshold)) != 1:
+            raise ValueError("give exactly one of keep, per_row and threshold")
+        if keep is not None:
+            return _lib.SM_PRUNE_GLOBAL_TOPK, int(keep), 0.0
+        if per_row is not None:
+            return _lib.SM_PRUNE_ROW_TOPK, int(per_row), 0.0
+        return _lib.SM_PRUNE_THRESHOLD, 0, float(threshold)
+
+    def prune_mask(self, keep=None, per_row=None, threshold=None, stream=None):
+        """The mask of the terms to keep (sm_prune_mask; the header states the rule on the values'
+        bits): a new uint8 tensor of nnz ones and zeros in CSR order on the matrix's device, for the
+        stored values of any matrix.  Exactly one of `keep` (the number of terms of greatest |value|
+        of the whole matrix), `per_row` (of every row) and `threshold` (keep |value| >= threshold).
+        Ties go to the earlier stored term; a NaN is kept first.  Synchronises `stream` (None: the
+        current torch stream)."""
+        import torch
+        h = self._require()
+        mode, count, thr = self._prune_args(keep, per_row, threshold)
+        mask = torch.empty(self._nnz(), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        st = self._L.sm_prune_mask(h, mode, count, thr, _ptr(mask) if mask.numel() else 0, None,
+                                   _stream_of(mask, stream))
+        check(st, "sm_prune_mask")
+        return mask
+
+    def masked(self, keep, opts: Optional[dict] = None, stream=None) -> "SparseMatrix":
+        """A new, independent matrix holding the terms whose keep[e] != 0, in stored order
+        (sm_create_masked), compacted on the device; the layouts are those from_csr builds from the
+        compacted arrays with the same `opts`.  `keep`: nnz uint8 elements on the matrix's device.
+        A table matrix gives a table matrix (same table, the kept terms' ids).  The result remembers
+        every term's index in this matrix (source_terms_device); built with
+        ``opts={"updatable": 1}`` it takes values laid out for this matrix (sm_set_values with
+        SM_VALUES_SOURCE).  Synchronises `stream` (None: the current torch stream)."""
+        import torch
+        h0 = self._require()
+        nnz = self._nnz()
+        if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype != torch.uint8:
+            raise TypeError("keep must be a CUDA (HIP) uint8 torch tensor")
+        if keep.dim() != 1 or keep.numel() != nnz or (nnz > 1 and keep.stride(0) != 1):
+            raise ValueError(f"keep must be a unit-stride 1-D tensor of nnz = {nnz} elements")
+        if keep.device.index != self.device:
+            raise ValueError("keep must be on the matrix's device")
+        p = SparseMatrix(device=self.device)
+        o = _lib.build_opts(**(opts or {}))
+        h = C.c_void_p()
+        st = self._L.sm_create_masked(h0, _ptr(keep) if nnz else 0, C.byref(o), _stream_of(self, stream), C.byref(h))
+        check(st, "masked")
+        p._h = h
+        return p
+
+    def pruned(self, keep=None, per_row=None, threshold=None, opts: Optional[dict] = None,
+               stream=None) -> "SparseMatrix":
+        """prune_mask, then masked, without the mask leaving the library (sm_create_pruned):
+        ``P = M.pruned(keep=M.nnz // 2, opts={"updatable": 1})``.  Arguments as for those two."""
+        h0 = self._require()
+        mode, count, thr = self._prune_args(keep, per_row, threshold)
+        p = SparseMatrix(device=self.device)
+        o = _lib.build_opts(**(opts or {}))
+        h = C.c_void_p()
+        st = self._L.sm_create_pruned(h0, mode, count, thr, C.byref(o), _stream_of(self, stream), C.byref(h))
+        check(st, "pruned")
+        p._h = h
+        return p
+
+    def source_terms_device(self, stream=None):
+        """For a matrix made by masked / pruned (or transposed with ``opts={"updatable": 1}``):
+        terms[e] = the CSR index, in the matrix it was made from, of this matrix's term e
+        (sm_copy_source_terms_device) -- a new int32 tensor of nnz elements on the matrix's device,
+        copied on `stream`.  ``state[terms.long()]`` gathers per-term state of the source."""
+        import torch
+        h = self._require()
+        t = torch.empty(self._nnz(), dtype=torch.int32, device=torch.device("cuda", self.device))
+        check(self._L.sm_copy_source_terms_device(h, _ptr(t) if t.numel() else 0, _stream_of(t, stream)),
+              "sm_copy_source_terms_device")
+        return t
+
     def csr_device(self, stream=None):
         """(row_ptr, col_idx, val): new torch tensors on the matrix's device holding its CSR
         (sm_copy_csr_device; int32, int32, float32), copied on `stream` (None: the current
