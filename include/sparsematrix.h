@@ -571,6 +571,49 @@ SM_API sm_status sm_create_pruned(const sm_matrix *src, sm_prune_mode mode, int6
                                   const sm_build_opts *opts, sm_stream stream, sm_matrix **out);
 SM_API sm_status sm_copy_source_terms_device(const sm_matrix *m, int32_t *d_terms, sm_stream stream);
 
+/* ---- from dense weights: select and compact on the device ---------------------------------------
+ * The entrance of the pipeline: a matrix from a dense fp32 weight matrix on the device, without
+ * the caller composing abs / sort / compare / to-CSR, and with the rule stated bit for bit.
+ * d_w is B itself, in sm_create_from_csr's orientation: n_rows x n_cols, row-major on `device`,
+ * element (r, c) at d_w[r * ld + c], ld >= n_cols (ld is not looked at when n_rows <= 1).  Any
+ * 4-byte alignment and any ld are correct; placement only selects the kernel (16-byte loads where
+ * d_w is 16-byte aligned and either ld == n_cols or ld and n_cols are multiples of 4).  The
+ * padding columns [n_cols, ld) are never read; d_w is never written.
+ *
+ * The rule is sm_prune_mask's, with no new wording: the dense matrix stands for the full CSR in
+ * which every one of its E = n_rows * n_cols elements is a stored term -- term index
+ * i = r * n_cols + c, columns ascending, zeros included -- and `mode`, `count`, `threshold` select
+ * exactly the terms sm_prune_mask would keep on that matrix: keys are bits & 0x7FFFFFFF, ties go
+ * to the lower i, a NaN is kept first.  So SM_PRUNE_THRESHOLD with the smallest subnormal (key 1)
+ * keeps exactly the non-zeros, threshold 0 keeps every element, and a top-k whose count exceeds
+ * the number of non-zeros keeps zeros, lowest index first.
+ *
+ * The result is the matrix sm_create_from_csr_device_ex builds from the kept terms (rows with
+ * ascending columns, values as bit copies) with the same `opts`: sm_equal, sm_layout_digest,
+ * sm_info (device_bytes aside), sm_built_on_device and every product of every sm_algo, bit for
+ * bit.  opts->updatable is honoured; opts->table_updatable = 1 is SM_ERR_INVALID_ARG.  No source
+ * map is kept (sm_copy_source_terms_device: SM_ERR_NOT_SUPPORTED): a term's origin is its
+ * (row, column).  The full matrix, or an E-sized int32 / float copy of it, is never formed.
+ *
+ * Checks, in this order and before any device work: a null `out`; mode, count and threshold as
+ * for sm_prune_mask; n_rows < 0, n_cols < 0, or ld < n_cols with n_rows > 1 (SM_ERR_INVALID_ARG);
+ * the options; n_rows or n_cols >= 2^31 - 1, E > 2^32 - 1 (the select's 32-bit bins count every
+ * element), or a kept count known in advance -- SM_PRUNE_GLOBAL_TOPK: min(count, E),
+ * SM_PRUNE_ROW_TOPK: n_rows * min(count, n_cols) -- past sm_create_from_csr's nnz limit
+ * (SM_ERR_TOO_LARGE); a null d_w with E > 0.  SM_PRUNE_THRESHOLD learns its kept count from the
+ * count pass and returns SM_ERR_TOO_LARGE there, with nothing leaked.  E = 0: an empty matrix,
+ * nothing launched, d_w may be NULL.  count = 0: an empty matrix of the given shape.
+ *
+ * Deterministic: integers only, integer atomics on counters only, every launch geometry a
+ * function of (n_rows, n_cols, the alignment class of d_w and ld).  The call allocates its
+ * scratch and synchronises `stream`: it is not for graph capture.
+ * Scratch while selecting: a byte mask, 1 byte per dense element (rounded up to 2048), 8 bytes per
+ * 2048 elements of chunk counts and bases, 4 KiB of select state + hipCUB's scan storage. */
+SM_API sm_status sm_create_from_dense_device(const float *d_w, int64_t n_rows, int64_t n_cols, int64_t ld,
+                                             sm_prune_mode mode, int64_t count, float threshold,
+                                             int32_t device, sm_stream stream,
+                                             const sm_build_opts *opts /* NULL: defaults */, sm_matrix **out);
+
 /* Destroy: sparse-matrix.cc:9-18 (frees host and device storage). */
 SM_API void sm_destroy(sm_matrix *m);
 
@@ -641,6 +684,21 @@ SM_API sm_status sm_copy_csr_device(const sm_matrix *m, int32_t *d_row_ptr, int3
  * are zeroed.  Decoded on the device.  A (row, column) stored more than once gets the value
  * of its last stored term (the products add every one). */
 SM_API sm_status sm_to_dense(const sm_matrix *m, float *out, int32_t stride, sm_trans trans);
+
+/* sm_to_dense with a device output: NoTrans writes S (s_rows x s_cols, B transposed), Trans
+ * writes S^T = B (n_rows x n_cols), row-major with rows `ld` apart (ld >= the row width, 64-bit).
+ * d_out is on the matrix's device at any 4-byte alignment.  Exactly the columns [0, width) of
+ * each output row are written -- zeros where B stores nothing; the padding columns [width, ld)
+ * and everything outside are untouched (the library's operand rule, not sm_to_dense's whole-stride
+ * memset).  A (row, column) stored more than once gets its last stored term's value,
+ * deterministically: matrices whose rows all strictly ascend (found when the matrix is made)
+ * scatter one thread per term, others one thread per row in stored order.  Asynchronous on
+ * `stream`: no allocation, no host synchronisation, no matrix scratch, the matrix only read -- it
+ * can be captured in a HIP graph, and calls from several streams need no ordering.  An empty
+ * output is SM_OK with nothing launched.  SM_ERR_INVALID_ARG, before any device work: a null
+ * matrix, a bad `trans`, a null d_out with a non-empty output, ld < width. */
+SM_API sm_status sm_to_dense_device(const sm_matrix *m, float *d_out, int64_t ld, sm_trans trans,
+                                    sm_stream stream);
 
 /* operator== (sparse-matrix.cc:197-207) on semantic content: shape, stored
  * (row, col, value) triples and, for codebook matrices, the table. */

@@ -938,6 +938,62 @@ sm_status sm_create_pruned(const sm_matrix *src, sm_prune_mode mode, int64_t cou
     return create_masked(src, d_keep, opts, s, out);
 }
 
+// The entrance of the pipeline: select and compact straight from a dense device matrix
+// (kernels_dense.hip), then the device-CSR constructors' tail, as create_masked ends.
+sm_status sm_create_from_dense_device(const float *d_w, int64_t n_rows, int64_t n_cols, int64_t ld, sm_prune_mode mode,
+                                      int64_t count, float threshold, int32_t device, sm_stream stream,
+                                      const sm_build_opts *opts, sm_matrix **out) {
+    if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (const sm_status st = check_prune_args(mode, count, threshold)) return st;
+    if (n_rows < 0 || n_cols < 0) return fail(SM_ERR_INVALID_ARG, "negative size");
+    if (n_rows > 1 && ld < n_cols)
+        return fail(SM_ERR_INVALID_ARG, "sm_create_from_dense_device: ld %lld < n_cols %lld", (long long)ld, (long long)n_cols);
+    if (const sm_status st = check_opts(opts)) return st;   // table_updatable among them
+    if (const sm_status st = check_sizes(n_rows, n_cols, 0)) return st;
+    // n_rows, n_cols < 2^31: the product fits 64 bits.  The 32-bit bins of the select count E.
+    const uint64_t E = (uint64_t)n_rows * (uint64_t)n_cols;
+    if (E > 0xFFFFFFFFull)
+        return fail(SM_ERR_TOO_LARGE, "sm_create_from_dense_device: %llu elements, at most 2^32 - 1", (unsigned long long)E);
+    int64_t known = -1;   // the kept count where the arguments give it
+    if (mode == SM_PRUNE_GLOBAL_TOPK) known = (int64_t)std::min<uint64_t>((uint64_t)count, E);
+    if (mode == SM_PRUNE_ROW_TOPK) known = n_rows * std::min(count, n_cols);
+    if (known >= 0)
+        if (const sm_status st = check_sizes(n_rows, n_cols, known)) return st;
+    if (E > 0 && !d_w) return fail(SM_ERR_INVALID_ARG, "sm_create_from_dense_device: null matrix pointer");
+    sm_status st = check_device(device);
+    if (st != SM_OK) return st;
+    DeviceGuard g(device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    DevScratch tmp;
+    uint8_t *d_keep = nullptr;
+    uint32_t *d_base = nullptr;
+    int64_t kept = 0;
+    if (E > 0 && known != 0) {
+        const hipError_t e = dense_mask_device(d_w, n_rows, n_cols, ld, mode, count, threshold, tmp, &d_keep, &d_base, &kept, s);
+        if (e != hipSuccess) return hip_fail(e, "sm_create_from_dense_device (select)");
+        if (const sm_status sz = check_sizes(n_rows, n_cols, kept)) return sz;   // SM_PRUNE_THRESHOLD: known only now
+    }
+    auto m = new_matrix(device, opts);
+    set_shape(m.get(), n_rows, n_cols, kept);
+    st = alloc_csr(m.get());
+    if (st == SM_OK) {
+        const hipError_t e = kept > 0 ? launch_dense_fill(d_w, n_rows, n_cols, ld, d_keep, d_base, m->d_row_ptr, m->d_col, m->d_val, s)
+                                      : hipMemsetAsync(m->d_row_ptr, 0, (size_t)(n_rows + 1) * sizeof(int32_t), s);
+        if (e != hipSuccess) st = hip_fail(e, "sm_create_from_dense_device (fill)");
+    }
+    if (st == SM_OK) st = finish_from_device_csr(m.get(), s, false);   // synchronises s: the scratch is free to go
+    if (st != SM_OK) {
+        (void)hipStreamSynchronize(s);
+        m.reset();
+        (void)hipGetLastError();   // a failed allocation leaves no sticky error behind
+        return st;
+    }
+    *out = m.release();
+    return SM_OK;
+}
+
 sm_status sm_copy_source_terms_device(const sm_matrix *m, int32_t *d_terms, sm_stream stream) {
     if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
     if (!m->has_src_term)
@@ -1212,6 +1268,29 @@ sm_status sm_to_dense(const sm_matrix *m, float *out, int32_t stride, sm_trans t
                                  trans == SM_TRANS, 0);
     if (e == hipSuccess) e = hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "sm_to_dense");
+    return SM_OK;
+}
+
+// The exit of the pipeline: sm_to_dense's orientations into a device buffer, asynchronously, the
+// matrix only read and nothing allocated.
+sm_status sm_to_dense_device(const sm_matrix *m, float *d_out, int64_t ld, sm_trans trans, sm_stream stream) {
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (trans != SM_NO_TRANS && trans != SM_TRANS) return fail(SM_ERR_INVALID_ARG, "bad trans");
+    const int64_t out_rows = trans == SM_TRANS ? m->s_cols : m->s_rows;
+    const int64_t width = trans == SM_TRANS ? m->s_rows : m->s_cols;
+    if (out_rows == 0 || width == 0) return SM_OK;
+    if (!d_out) return fail(SM_ERR_INVALID_ARG, "sm_to_dense_device: null output");
+    if (ld < width) return fail(SM_ERR_INVALID_ARG, "sm_to_dense_device: ld %lld < %lld", (long long)ld, (long long)width);
+    DeviceGuard g(m->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = launch_dense_zero(d_out, out_rows, width, ld, s);
+    if (e == hipSuccess && m->nnz > 0)
+        e = m->rows_ascend ? launch_scatter_terms((int32_t)m->n_rows, m->nnz, m->d_row_ptr, m->d_col, m->d_val, d_out, ld,
+                                                  trans == SM_TRANS, s)
+                           : launch_scatter_dense((int32_t)m->n_rows, m->d_row_ptr, m->d_col, m->d_val, d_out, ld,
+                                                  trans == SM_TRANS, s);
+    if (e != hipSuccess) return hip_fail(e, "sm_to_dense_device");
     return SM_OK;
 }
 

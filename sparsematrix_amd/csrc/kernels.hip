@@ -470,6 +470,17 @@ __global__ __launch_bounds__(256) void validate_kernel(int32_t n_rows, int32_t n
         if (i < nnz) {
             const int32_t c = col[i];
             if (c < 0 || c >= n_cols) f |= 8;
+            // A descent inside a row (kCsrNotAscending).  Ascending rows descend only where the
+            // next row starts, about once a row: only there is row_ptr searched for i + 1.
+            if (i + 1 < nnz && c >= col[i + 1]) {
+                int32_t lo = 0, hi = n_rows + 1;   // the first index whose pointer is >= i + 1
+                while (lo < hi) {
+                    const int32_t mid = lo + ((hi - lo) >> 1);
+                    if (rp[mid] < (int32_t)(i + 1)) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo > n_rows || rp[lo] != (int32_t)(i + 1)) f |= kCsrNotAscending;
+            }
         }
     }
     if (f) atomicOr(flag, f);

@@ -938,6 +938,13 @@ sm_status finish_from_host_csr(sm_matrix *m, const int32_t *rp, const int32_t *c
         SM_TRY_HIP(hipMemcpy(m->d_col, col, (size_t)m->nnz * 4, hipMemcpyHostToDevice));
         SM_TRY_HIP(hipMemcpy(m->d_val, val, (size_t)m->nnz * 4, hipMemcpyHostToDevice));
     }
+    m->rows_ascend = true;
+    for (int64_t r = 0; r < m->n_rows && m->rows_ascend; r++)
+        for (int32_t e = rp[r] + 1; e < rp[r + 1]; e++)
+            if (col[e - 1] >= col[e]) {
+                m->rows_ascend = false;
+                break;
+            }
     st = upload_plan(m, rp);
     if (st != SM_OK) return st;
     return build_host_layouts(m, rp, col, [val](const float *&v) { v = val; return SM_OK; }, true);
@@ -963,7 +970,8 @@ sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell) {
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
     if (e != hipSuccess) return hip_fail(e, "sm_create_from_csr_device");
-    if (flag) return fail(SM_ERR_INVALID_MATRIX, "device CSR failed validation (flags 0x%x)", flag);
+    if (flag & kCsrInvalid) return fail(SM_ERR_INVALID_MATRIX, "device CSR failed validation (flags 0x%x)", flag & kCsrInvalid);
+    m->rows_ascend = !(flag & kCsrNotAscending);
     st = upload_plan(m, rp.data());
     const bool xband = want_xband(m);
     // The column relabeling and the sorted sliced ELL on the device (builddev.hip) where they

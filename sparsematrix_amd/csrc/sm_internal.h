@@ -509,6 +509,27 @@ hipError_t launch_prune_compact(int64_t n_rows, int64_t nnz, const uint8_t *keep
                                 const int32_t *rp, const int32_t *col, const float *val, const uint8_t *ids,
                                 int32_t *new_rp, int32_t *new_col, float *new_val, int32_t *src_term, uint8_t *new_ids,
                                 bool any_kept, hipStream_t s);
+// From and to dense weights (kernels_dense.hip).  dense_mask_device: sm_prune_mask's rule for the
+// full CSR that W stands for (n_rows x n_cols at w[r * ld + c], E = n_rows * n_cols in
+// [1, 2^32 - 1], the arguments checked by the caller, a top-k count >= 1) into a byte mask over
+// whole chunks of kSddmmChunk elements in i = r * n_cols + c order (zero past E) and base[ch], the
+// kept elements before chunk ch (n_chunks + 1 entries), both allocated from `t`; *kept = their
+// number.  Synchronises `s`; leaves no sticky HIP error on failure.  launch_dense_fill: the
+// compaction by that mask into rp (n_rows + 1), col and val (kept < 2^31 entries).
+// launch_dense_zero: zeros over columns [0, width) of `rows` rows of `out`.  launch_scatter_terms:
+// launch_scatter_dense's stores by one thread per term, for a matrix whose rows strictly ascend.
+hipError_t dense_mask_device(const float *w, int64_t n_rows, int64_t n_cols, int64_t ld, sm_prune_mode mode,
+                             int64_t count, float threshold, DevScratch &t, uint8_t **keep, uint32_t **base,
+                             int64_t *kept, hipStream_t s);
+hipError_t launch_dense_fill(const float *w, int64_t n_rows, int64_t n_cols, int64_t ld, const uint8_t *keep,
+                             const uint32_t *base, int32_t *rp, int32_t *col, float *val, hipStream_t s);
+hipError_t launch_dense_zero(float *out, int64_t rows, int64_t width, int64_t ld, hipStream_t s);
+hipError_t launch_scatter_terms(int32_t n_rows, int64_t nnz, const int32_t *rp, const int32_t *col, const float *val,
+                                float *out, int64_t ld, bool b_layout, hipStream_t s);
+// *d_flag |= 1, 2, 4 (row_ptr: start, end, order or range), 8 (a column out of range): the CSR is
+// invalid; |= kCsrNotAscending where some row has col[e] >= col[e + 1]: valid, but see
+// sm_matrix::rows_ascend.
+constexpr int32_t kCsrInvalid = 15, kCsrNotAscending = 16;
 hipError_t launch_validate(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t *rp,
                            const int32_t *col, int32_t *d_flag, hipStream_t s);
 // Dense decode: out is zeroed by the caller.  b_layout: out[row*stride+col]
@@ -539,6 +560,9 @@ struct sm_matrix {
     // it); mem.bytes is sm_info.device_bytes.  ~sm_matrix frees them all.
     smamd::DevMem mem;
     uint32_t built_on_device = 0;              // SM_BUILT_DEV_* of the layouts the device builders made
+    // Every row's columns strictly ascend (found by the constructors' validation): no (row, column)
+    // is stored twice, so sm_to_dense_device may scatter the terms in any order.
+    bool rows_ascend = false;
     ~sm_matrix();
     // Reference encoding (only for matrices built by sm_create_from_dense_index).
     bool has_ref = false;

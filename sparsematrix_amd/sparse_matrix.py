@@ -211,6 +211,47 @@ class SparseMatrix:
         return self
 
     @classmethod
+    def from_dense(cls, W, keep=None, per_row=None, threshold=None, opts: Optional[dict] = None,
+                   stream=None) -> "SparseMatrix":
+        """B from a dense float32 weight matrix on the device, selected and compacted there
+        (sm_create_from_dense_device): exactly one of `keep` (the number of elements of greatest
+        |value| of the whole matrix), `per_row` (of every row) and `threshold` (keep |value| >=
+        threshold; the smallest subnormal keeps exactly the non-zeros, 0 keeps every element).  The
+        rule is prune_mask's, on the full matrix in which every element of `W` is a stored term:
+        ties go to the lower (row, column), a NaN is kept first.  The result is the matrix from_csr
+        builds from the kept terms with the same `opts` (``{"updatable": 1}`` for fine-tuning).
+        `W` is a 2-D float32 CUDA (HIP) tensor with ``stride(1) == 1``; ``stride(0)`` may exceed
+        the row width, so padded and row-sliced views are read in place -- the padding is never
+        read and `W` never written.  Nothing is copied silently: any other layout raises.
+        Synchronises `stream` (None: the current torch stream)."""
+        mode, count, thr = cls._prune_args(keep, per_row, threshold)
+        if isinstance(W, np.ndarray) or not hasattr(W, "is_cuda"):
+            raise TypeError("from_dense takes a torch tensor on the device; for host data build the CSR "
+                            "(e.g. scipy.sparse.csr_matrix) and use from_csr")
+        import torch
+        if not W.is_cuda:
+            raise TypeError("W is a host tensor: move it with W.cuda(), or build the CSR and use from_csr")
+        if W.dtype != torch.float32:
+            raise TypeError(f"W must be float32, got {W.dtype}: convert with W.float()")
+        if W.dim() != 2:
+            raise ValueError(f"W must be 2-D (n_rows x n_cols), got {W.dim()}-D: use W.reshape(n_rows, -1)")
+        n_rows, n_cols = int(W.shape[0]), int(W.shape[1])
+        if W.numel() and n_cols > 1 and W.stride(1) != 1:
+            raise ValueError("W must be row-major (stride(1) == 1): use W.contiguous() (a transposed view "
+                             "would be read as its transpose's memory)")
+        ld = int(W.stride(0)) if n_rows > 1 and W.numel() else n_cols   # an empty tensor's strides say nothing
+        if ld < n_cols:
+            raise ValueError(f"W has stride(0) = {ld} < {n_cols} columns (an expanded view?): use W.contiguous()")
+        self = cls(device=W.device.index)
+        o = _lib.build_opts(**(opts or {}))
+        h = C.c_void_p()
+        st = self._L.sm_create_from_dense_device(_ptr(W) if W.numel() else 0, n_rows, n_cols, ld, mode, count, thr,
+                                                 self.device, _stream_of(W, stream), C.byref(o), C.byref(h))
+        check(st, "from_dense")
+        self._h = h
+        return self
+
+    @classmethod
     def from_csr_ids(cls, row_ptr, col_idx, ids, table, n_cols: int, device: int = 0,
                      opts: Optional[dict] = None) -> "SparseMatrix":
         """A table matrix (sm_create_from_csr_ids): the terms of B (n_rows x n_cols) as
@@ -398,7 +439,9 @@ class SparseMatrix:
 
     def CopyTo(self, density_matrix: Optional[np.ndarray], stride: int,
                trans: int = SblasNoTrans) -> np.ndarray:
-        """sparse-matrix.cc:101-137: decode into a dense float matrix (host)."""
+        """sparse-matrix.cc:101-137: decode into a dense float matrix (host).  NoTrans (the
+        default) writes S, Trans writes S^T = B; dense_device below is the device form, whose
+        default is the other way round: B."""
         inf = self.info()
         nr = inf["s_cols"] if trans else inf["s_rows"]
         if density_matrix is None:
@@ -409,6 +452,34 @@ class SparseMatrix:
         if out.size < nr * stride:
             raise ValueError("output smaller than rows * stride")
         check(self._L.sm_to_dense(self._h, _ptr(out), stride, int(trans)), "CopyTo")
+        return out
+
+    def dense_device(self, out=None, trans: bool = True, stream=None):
+        """CopyTo with a device output (sm_to_dense_device).  Mind the orientation: CopyTo's
+        default (NoTrans) is the reference's S view, this method's default (``trans=True``) is
+        B = S^T, the ``n_rows x n_cols`` matrix from_csr and from_dense take, so that
+        ``from_dense(M.dense_device(), ...)`` round-trips; ``trans=False`` gives the S view
+        (``n_cols x n_rows``).  `out`: None for a new tensor, or a 2-D float32 tensor on the
+        matrix's device with ``stride(1) == 1`` and at least that many rows and columns (a padded
+        or row-sliced view is fine): the leading rows x columns are written in place -- zeros where
+        nothing is stored -- and its padding stays untouched.  A (row, column) stored more than
+        once gets its last stored term's value.  Asynchronous on `stream` (None: the current torch
+        stream); nothing is allocated by the library, so the call can be captured in a graph."""
+        import torch
+        h = self._require()
+        n_rows, n_cols = self._dims()
+        rows, cols = (n_rows, n_cols) if trans else (n_cols, n_rows)
+        if out is None:
+            out = torch.empty((rows, cols), dtype=torch.float32, device=torch.device("cuda", self.device))
+        else:
+            _check_dev_2d(out, rows, cols, "out")
+            if out.device.index != self.device:
+                raise ValueError("out must be on the matrix's device")
+        ld = int(out.stride(0)) if out.shape[0] > 1 else max(cols, 1)
+        if rows and cols:
+            st = self._L.sm_to_dense_device(h, _ptr(out), ld, SM_TRANS if trans else SM_NO_TRANS,
+                                            _stream_of(out, stream))
+            check(st, "dense_device")
         return out
 
     def __eq__(self, other) -> bool:
