@@ -614,6 +614,57 @@ SM_API sm_status sm_create_from_dense_device(const float *d_w, int64_t n_rows, i
                                              int32_t device, sm_stream stream,
                                              const sm_build_opts *opts /* NULL: defaults */, sm_matrix **out);
 
+/* ---- the sum of two matrices: C = alpha A + beta B on the union of their patterns ----------------
+ * The one call that puts terms into a held matrix: the csrgeam of a sparse BLAS, the merge of a
+ * sparse delta into a sparse weight, and -- as sm_create_sum(A, 1, G, 0) -- the regrow step of
+ * dynamic sparse training.  sm_create_sum makes a new, independent matrix C of the operands' shape
+ * on their device; `a` and `b` are only read, and a == b is allowed.  The call allocates its own
+ * scratch and synchronises `stream`: it is not meant for graph capture.
+ *
+ * The pattern, on integers only:
+ *   Row r of C holds the union of the columns of row r of A and of row r of B, ascending; each
+ *   (row, column) is stored once.  A term stays a stored term whatever its value: explicit zeros
+ *   of either operand and sums that cancel to 0 are kept.  Nothing is dropped by value.
+ * The value of a term of C at (r, c), so that it can be restated bit for bit:
+ *   A's contribution is absent if A does not store (r, c) or alpha == 0 -- A's values are then
+ *     never read (the library's "alpha == 0 skips" rule: a NaN there does not reach C).  Otherwise
+ *     it is pa = a's bits as they are if alpha == 1, and pa = fl(alpha * a) in every other case.
+ *   B's contribution pb: the same with beta.
+ *   Both present: fl(pa + pb) -- two separately rounded products and one add, never a fused
+ *     multiply-add.  One present: its bits.  None present: +0.0.
+ *   Subnormals are kept.  A NaN result is a NaN where the rule gives one (Inf - Inf, 0 * Inf, a NaN
+ *     operand); its payload is the hardware's.
+ *   So sm_create_sum(A, 1, G, 0) is A's values, bit for bit, on the union pattern, the positions
+ *   only G stores at +0.0; (1, -1) is A - B; (0, 0) is the union pattern at +0.0.
+ * The source maps, always kept and counted in sm_info.device_bytes: for term e of C, terms_a[e] is
+ *   the CSR index of that position in A, or -1 where A does not store it; terms_b[e] the same for
+ *   B.  sm_copy_sum_terms_device copies them (nnz int32 each, on the matrix's device, asynchronous
+ *   on `stream`; either array may be NULL and is then skipped); SM_ERR_NOT_SUPPORTED on a matrix
+ *   sm_create_sum did not make; nnz == 0 is SM_OK with nothing launched.  There is no single source
+ *   term, so SM_VALUES_SOURCE stays SM_ERR_NOT_SUPPORTED on a sum matrix and
+ *   sm_copy_source_terms_device refuses it; state laid out for A is carried with terms_a.
+ * The result is the matrix sm_create_from_csr_device_ex builds from the restated (row_ptr, col_idx,
+ *   val) with the same `opts` (NULL: defaults): sm_equal, sm_layout_digest, sm_info (device_bytes
+ *   aside), sm_built_on_device and every product of every sm_algo, bit for bit.  opts->updatable is
+ *   honoured; opts->table_updatable = 1 is SM_ERR_INVALID_ARG.  Table sources and dense-index
+ *   (CopyForm) sources contribute their stored values; C is an ordinary CSR matrix
+ *   (sm_info.table_size and has_ref_stream are 0).
+ * Checks, in this order, the first five before any device work: a null `out`; a null `a` or `b`;
+ *   the options; differing n_rows / n_cols or differing devices (SM_ERR_INVALID_ARG); an operand
+ *   with a row whose columns do not strictly ascend (SM_ERR_NOT_SUPPORTED, the message names the
+ *   operand: such a row has no merge and no single source term).  After the count pass: a union
+ *   past sm_create_from_csr's nnz limit (SM_ERR_TOO_LARGE, nothing leaked; the row lengths sum to
+ *   at most nnzA + nnzB < 2^32 and are scanned in unsigned 32 bits).
+ * Deterministic: the structure is integers only, no atomics at all, every launch geometry a
+ *   function of (n_rows, nnzA, nnzB); C is a function of the operands, alpha and beta alone.
+ * Scratch while building: 8 bytes per term of A (the match word and its scan), 8 bytes per row
+ *   (the lengths and their scan) + hipCUB's scan storage.  B's terms need none. */
+SM_API sm_status sm_create_sum(const sm_matrix *a, float alpha, const sm_matrix *b, float beta,
+                               const sm_build_opts *opts /* NULL: defaults */, sm_stream stream,
+                               sm_matrix **out);
+SM_API sm_status sm_copy_sum_terms_device(const sm_matrix *m, int32_t *d_terms_a, int32_t *d_terms_b,
+                                          sm_stream stream);   /* either array may be NULL: skipped */
+
 /* Destroy: sparse-matrix.cc:9-18 (frees host and device storage). */
 SM_API void sm_destroy(sm_matrix *m);
 

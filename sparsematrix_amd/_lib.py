@@ -56,6 +56,7 @@ EXPORTS = (
     "sm_create_from_csr_ids_device", "sm_quantize_assign", "sm_quantize_update", "sm_create_quantized",
     "sm_prune_mask", "sm_create_masked", "sm_create_pruned", "sm_copy_source_terms_device",
     "sm_create_from_dense_device", "sm_to_dense_device",
+    "sm_create_sum", "sm_copy_sum_terms_device",
 )
 
 SM_UNIQUE_ID_BYTES = 128
@@ -183,6 +184,8 @@ def _declare(L):
         "sm_create_from_dense_device": ([_vp, _i64, _i64, _i64, C.c_int, _i64, _f32, _i32, _vp,
                                          C.POINTER(SmBuildOpts), C.POINTER(_vp)], C.c_int),
         "sm_to_dense_device": ([_vp, _vp, _i64, C.c_int, _vp], C.c_int),
+        "sm_create_sum": ([_vp, _f32, _vp, _f32, C.POINTER(SmBuildOpts), _vp, C.POINTER(_vp)], C.c_int),
+        "sm_copy_sum_terms_device": ([_vp, _vp, _vp, _vp], C.c_int),
         "sm_copy_table_device": ([_vp, _vp, _vp], C.c_int),
         "sm_copy_term_ids_device": ([_vp, _vp, _vp], C.c_int),
         "sm_sddmm_table": ([_vp, _i32, _f32, _vp, _i64, _vp, _i64, _f32, _vp, C.c_int, _vp], C.c_int),

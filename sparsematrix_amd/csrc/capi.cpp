@@ -994,6 +994,74 @@ sm_status sm_create_from_dense_device(const float *d_w, int64_t n_rows, int64_t 
     return SM_OK;
 }
 
+// C = alpha A + beta B on the union of the patterns (kernels_sum.hip): count, check the size, fill
+// the new matrix's arrays and maps, then the device-CSR constructors' tail, as create_masked ends.
+sm_status sm_create_sum(const sm_matrix *a, float alpha, const sm_matrix *b, float beta, const sm_build_opts *opts,
+                        sm_stream stream, sm_matrix **out) {
+    if (!out) return fail(SM_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (!a || !b) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (const sm_status st = check_opts(opts)) return st;   // table_updatable among them
+    if (a->n_rows != b->n_rows || a->n_cols != b->n_cols)
+        return fail(SM_ERR_INVALID_ARG, "sm_create_sum: a is %lld x %lld, b is %lld x %lld", (long long)a->n_rows,
+                    (long long)a->n_cols, (long long)b->n_rows, (long long)b->n_cols);
+    if (a->device != b->device)
+        return fail(SM_ERR_INVALID_ARG, "sm_create_sum: a is on device %d, b on device %d", a->device, b->device);
+    for (const sm_matrix *x : {a, b})
+        if (!x->rows_ascend)
+            return fail(SM_ERR_NOT_SUPPORTED, "sm_create_sum: a row of operand %s holds a descending step or a repeated "
+                                              "column: no merge and no single source term", x == a ? "a" : "b");
+    DeviceGuard g(a->device);
+    if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+    hipStream_t s = (hipStream_t)stream;
+    DevScratch tmp;
+    int32_t *d_m = nullptr, *d_S = nullptr, *d_rpc = nullptr;
+    uint64_t nnz_c = 0;
+    hipError_t e = sum_count_device(a->n_rows, a->nnz, b->nnz, a->d_row_ptr, a->d_col, b->d_row_ptr, b->d_col, tmp, &d_m,
+                                    &d_S, &d_rpc, &nnz_c, s);
+    if (e != hipSuccess) return hip_fail(e, "sm_create_sum (count)");
+    if (const sm_status st = check_sizes(a->n_rows, a->n_cols, (int64_t)nnz_c)) return st;   // nnz_c < 2^32
+    const int64_t nnz = (int64_t)nnz_c;
+    auto m = new_matrix(a->device, opts);
+    set_shape(m.get(), a->n_rows, a->n_cols, nnz);
+    sm_status st = alloc_csr(m.get());
+    m->has_sum_terms = true;
+    if (st == SM_OK && nnz > 0) {
+        e = m->mem.alloc(&m->d_sum_terms_a, nnz);
+        if (e == hipSuccess) e = m->mem.alloc(&m->d_sum_terms_b, nnz);
+        if (e != hipSuccess) st = hip_fail(e, "sm_create_sum (source maps)");
+    }
+    if (st == SM_OK) {
+        e = hipMemcpyAsync(m->d_row_ptr, d_rpc, (size_t)(a->n_rows + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && nnz > 0)
+            e = launch_sum_fill(a->n_rows, a->nnz, b->nnz, a->d_row_ptr, a->d_col, a->d_val, alpha, b->d_row_ptr, b->d_col,
+                                b->d_val, beta, d_m, d_S, d_rpc, m->d_col, m->d_val, m->d_sum_terms_a, m->d_sum_terms_b, s);
+        if (e != hipSuccess) st = hip_fail(e, "sm_create_sum (fill)");
+    }
+    if (st == SM_OK) st = finish_from_device_csr(m.get(), s, false);   // synchronises s: the scratch is free to go
+    if (st != SM_OK) {
+        (void)hipStreamSynchronize(s);
+        m.reset();
+        (void)hipGetLastError();   // a failed allocation leaves no sticky error behind
+        return st;
+    }
+    *out = m.release();
+    return SM_OK;
+}
+
+sm_status sm_copy_sum_terms_device(const sm_matrix *m, int32_t *d_terms_a, int32_t *d_terms_b, sm_stream stream) {
+    if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
+    if (!m->has_sum_terms)
+        return fail(SM_ERR_NOT_SUPPORTED, "sm_copy_sum_terms_device: the matrix holds no sum maps (sm_create_sum)");
+    if (m->nnz == 0) return SM_OK;
+    DeviceGuard g(m->device);
+    if (d_terms_a)
+        SM_TRY_HIP(hipMemcpyAsync(d_terms_a, m->d_sum_terms_a, (size_t)m->nnz * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_terms_b)
+        SM_TRY_HIP(hipMemcpyAsync(d_terms_b, m->d_sum_terms_b, (size_t)m->nnz * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SM_OK;
+}
+
 sm_status sm_copy_source_terms_device(const sm_matrix *m, int32_t *d_terms, sm_stream stream) {
     if (!m) return fail(SM_ERR_INVALID_ARG, "null matrix");
     if (!m->has_src_term)

@@ -526,6 +526,21 @@ hipError_t launch_dense_fill(const float *w, int64_t n_rows, int64_t n_cols, int
 hipError_t launch_dense_zero(float *out, int64_t rows, int64_t width, int64_t ld, hipStream_t s);
 hipError_t launch_scatter_terms(int32_t n_rows, int64_t nnz, const int32_t *rp, const int32_t *col, const float *val,
                                 float *out, int64_t ld, bool b_layout, hipStream_t s);
+// The sum of two matrices (kernels_sum.hip), both validated device CSRs of n_rows rows whose rows
+// strictly ascend.  sum_count_device: the match words of A's terms (m[i] = B's term index where B
+// stores the position, ~(the lower bound of the column in B's row) where not), their exclusive
+// scan S (nnz_a + 1 entries) and the union's row pointer rp_c (n_rows + 1 entries, formed in
+// unsigned 32 bits), all allocated from `t`; *nnz_c = the union's size, which the caller checks
+// before it reads rp_c as int32.  Synchronises `s`; leaves no sticky HIP error on failure.
+// launch_sum_fill: col_c, val_c (sm_create_sum's value rule) and both source maps, nnz_c entries
+// each, every one written once.
+hipError_t sum_count_device(int64_t n_rows, int64_t nnz_a, int64_t nnz_b, const int32_t *rp_a, const int32_t *col_a,
+                            const int32_t *rp_b, const int32_t *col_b, DevScratch &t, int32_t **m, int32_t **S,
+                            int32_t **rp_c, uint64_t *nnz_c, hipStream_t s);
+hipError_t launch_sum_fill(int64_t n_rows, int64_t nnz_a, int64_t nnz_b, const int32_t *rp_a, const int32_t *col_a,
+                           const float *val_a, float alpha, const int32_t *rp_b, const int32_t *col_b,
+                           const float *val_b, float beta, const int32_t *m, const int32_t *S, const int32_t *rp_c,
+                           int32_t *col_c, float *val_c, int32_t *terms_a, int32_t *terms_b, hipStream_t s);
 // *d_flag |= 1, 2, 4 (row_ptr: start, end, order or range), 8 (a column out of range): the CSR is
 // invalid; |= kCsrNotAscending where some row has col[e] >= col[e + 1]: valid, but see
 // sm_matrix::rows_ascend.
@@ -580,6 +595,11 @@ struct sm_matrix {
     // in the source's order reach it (SM_VALUES_SOURCE; sm_copy_source_terms_device reads it).
     int32_t *d_src_term = nullptr;
     bool has_src_term = false;   // (also true with nnz == 0, where there is nothing to allocate)
+    // Every matrix made by sm_create_sum: per term its CSR index in each operand, or -1 (nnz
+    // entries each; sm_copy_sum_terms_device reads them).  There is no single source, so
+    // has_src_term stays false.
+    int32_t *d_sum_terms_a = nullptr, *d_sum_terms_b = nullptr;
+    bool has_sum_terms = false;   // (also true with nnz == 0)
     // Table matrix (sm_create_from_csr_ids and its transposes): the terms' ids (nnz bytes, CSR
     // order) and the authoritative table (256 floats, zero past tab_size) on the device, and the
     // per-chunk partials of sm_sddmm_table (tab_chunks * kTablePartialStride floats), used in

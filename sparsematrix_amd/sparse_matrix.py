@@ -883,6 +883,45 @@ class SparseMatrix:
               "sm_copy_source_terms_device")
         return t
 
+    # ---- the sum of two matrices on the union of their patterns --------------------------------
+    def sum(self, other: "SparseMatrix", alpha: float = 1.0, beta: float = 1.0, opts: Optional[dict] = None,
+            stream=None) -> "SparseMatrix":
+        """``alpha * self + beta * other`` as a new, independent matrix on the union of the two
+        patterns (sm_create_sum; the header states the value rule bit for bit): every row holds the
+        union of the two rows' columns, ascending; a term is kept whatever its value; a coefficient
+        of 0 leaves that operand's values unread and one of 1 takes them as they are, so
+        ``A.sum(G, 1, 0)`` is A on the union pattern with the new positions at +0.0 (the regrow step
+        of dynamic sparse training).  Both operands' rows must strictly ascend, and they must share
+        shape and device; `other` may be `self`.  The layouts are those from_csr builds from the
+        summed arrays with the same `opts`; the result remembers where every term came from
+        (sum_terms_device).  Synchronises `stream` (None: the current torch stream)."""
+        h0 = self._require()
+        if not isinstance(other, SparseMatrix):
+            raise TypeError("other must be a SparseMatrix")
+        h1 = other._require()
+        c = SparseMatrix(device=self.device)
+        o = _lib.build_opts(**(opts or {}))
+        h = C.c_void_p()
+        st = self._L.sm_create_sum(h0, float(alpha), h1, float(beta), C.byref(o), _stream_of(self, stream), C.byref(h))
+        check(st, "sum")
+        c._h = h
+        return c
+
+    def sum_terms_device(self, stream=None):
+        """For a matrix made by sum: ``(terms_a, terms_b)``, two new int32 tensors of nnz elements on
+        the matrix's device, copied on `stream` (sm_copy_sum_terms_device).  terms_a[e] is the CSR
+        index, in the first operand, of this matrix's term e, or -1 where that operand does not
+        store the position; terms_b the same for the second operand."""
+        import torch
+        h = self._require()
+        dev = torch.device("cuda", self.device)
+        n = self._nnz()
+        ta = torch.empty(n, dtype=torch.int32, device=dev)
+        tb = torch.empty(n, dtype=torch.int32, device=dev)
+        check(self._L.sm_copy_sum_terms_device(h, _ptr(ta) if n else 0, _ptr(tb) if n else 0, _stream_of(ta, stream)),
+              "sm_copy_sum_terms_device")
+        return ta, tb
+
     def csr_device(self, stream=None):
         """(row_ptr, col_idx, val): new torch tensors on the matrix's device holding its CSR
         (sm_copy_csr_device; int32, int32, float32), copied on `stream` (None: the current
