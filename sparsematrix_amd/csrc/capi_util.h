@@ -1,5 +1,5 @@
-// capi_util.h -- what the host files of the C ABI (capi.cpp, layouts.cpp, multi.cpp) share:
-// the error reporting behind sm_last_error, the device guard and the post-launch check.
+// capi_util.h -- what the host files of the C ABI (capi.cpp, create.cpp, layouts.cpp, multi.cpp)
+// share: the error reporting behind sm_last_error, the device guard and the post-launch check.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,11 +22,14 @@ inline sm_status hip_fail(hipError_t e, const char *what) {
         if (e_ != hipSuccess) return smamd::hip_fail(e_, #call);   \
     } while (0)
 
-// Makes `dev` current for the scope and restores the caller's device.
+// Makes `dev` current for the scope and restores the caller's device.  Default-constructed it
+// does nothing until enter() (a constructor checks the device's number first: create.cpp).
 struct DeviceGuard {
     int prev = -1;
     hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
+    DeviceGuard() = default;
+    explicit DeviceGuard(int dev) { enter(dev); }
+    void enter(int dev) {
         if (hipGetDevice(&prev) != hipSuccess) prev = -1;
         if (prev != dev) err = hipSetDevice(dev);
     }

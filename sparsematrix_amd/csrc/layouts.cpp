@@ -1,6 +1,6 @@
 // layouts.cpp -- what decides and builds a matrix's layouts, on the host side: the resolved
 // options, the cost models, the want_* decisions (each reads what was built before it, so their
-// order is significant), the upload_* builders and the two tails the constructors of capi.cpp
+// order is significant), the upload_* builders and the two tails the constructors of create.cpp
 // end in.  The device builders are builddev.hip and builddev_gcb.hip.
 #include <hip/hip_runtime.h>
 
@@ -909,11 +909,16 @@ sm_status alloc_csr(sm_matrix *m) {
 
 // The host builders, in the one order both constructor tails run them: each want_* reads what
 // was built before it.  `values(val)` makes the CSR values readable on the host at `val` before
-// the first builder that stores them (the device tail fetches them then, once).
+// the first builder that stores them (the device tail fetches them then, once).  `ids` / `table`:
+// a table matrix's own, on the host, which codebook_source hands a table_updatable matrix's
+// builders; the matrix points at them for this call only.
 template <class V>
-static sm_status build_host_layouts(sm_matrix *m, const int32_t *rp, const int32_t *col, V &&values, bool exact_sell) {
+static sm_status build_host_layouts(sm_matrix *m, const int32_t *rp, const int32_t *col, V &&values, bool exact_sell,
+                                    const uint8_t *ids, const float *table) {
     sm_status st = SM_OK;
     const float *val = nullptr;
+    m->build_ids = ids;
+    m->build_table = table;
     if (st == SM_OK && want_xband(m)) st = values(val);
     if (st == SM_OK && want_xband(m)) st = upload_xband(m, rp, col, val, xband_kind_setting(m));
     if (st == SM_OK && want_sweep(m)) st = values(val);
@@ -927,10 +932,13 @@ static sm_status build_host_layouts(sm_matrix *m, const int32_t *rp, const int32
     if (st == SM_OK && want_merge_stage(m)) st = upload_merge_stage(m, rp, col, val);
     if (st == SM_OK && exact_sell && want_exact_sell(m)) st = values(val);
     if (st == SM_OK && exact_sell && want_exact_sell(m)) st = upload_exact_sell(m, rp, col, val);
+    m->build_ids = nullptr;
+    m->build_table = nullptr;
     return st;
 }
 
-sm_status finish_from_host_csr(sm_matrix *m, const int32_t *rp, const int32_t *col, const float *val) {
+sm_status finish_from_host_csr(sm_matrix *m, const int32_t *rp, const int32_t *col, const float *val, const uint8_t *ids,
+                               const float *table) {
     sm_status st = alloc_csr(m);
     if (st != SM_OK) return st;
     SM_TRY_HIP(hipMemcpy(m->d_row_ptr, rp, (size_t)(m->n_rows + 1) * 4, hipMemcpyHostToDevice));
@@ -947,7 +955,7 @@ sm_status finish_from_host_csr(sm_matrix *m, const int32_t *rp, const int32_t *c
             }
     st = upload_plan(m, rp);
     if (st != SM_OK) return st;
-    return build_host_layouts(m, rp, col, [val](const float *&v) { v = val; return SM_OK; }, true);
+    return build_host_layouts(m, rp, col, [val](const float *&v) { v = val; return SM_OK; }, true, ids, table);
 }
 
 sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell) {
@@ -1077,7 +1085,18 @@ sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell) {
         hipError_t e3 = hipSuccess;
         if (nnz) e3 = hipMemcpy(ch.data(), m->d_col, (size_t)nnz * 4, hipMemcpyDeviceToHost);
         st = e3 == hipSuccess ? SM_OK : hip_fail(e3, "copy CSR columns for the layout builder");
-        if (st == SM_OK) st = build_host_layouts(m, rp.data(), ch.data(), values, exact_sell);
+        // A table_updatable matrix's builders take its own ids and table (codebook_source): 1 byte
+        // per term and the table come down once; `s` is synchronised above.
+        std::vector<uint8_t> h_ids;
+        std::vector<float> h_tab;
+        if (st == SM_OK && m->is_table && m->opts.table_updatable) {
+            h_ids.resize((size_t)nnz);
+            h_tab.resize(256);
+            if (nnz) e3 = hipMemcpy(h_ids.data(), m->d_tab_ids, (size_t)nnz, hipMemcpyDeviceToHost);
+            if (e3 == hipSuccess) e3 = hipMemcpy(h_tab.data(), m->d_tab, 256 * sizeof(float), hipMemcpyDeviceToHost);
+            if (e3 != hipSuccess) st = hip_fail(e3, "copy the table and its ids for the layout builder");
+        }
+        if (st == SM_OK) st = build_host_layouts(m, rp.data(), ch.data(), values, exact_sell, h_ids.data(), h_tab.data());
     }
     return st;
 }

@@ -400,7 +400,7 @@ int devbuild_codebook(const float *d_val, int64_t n, std::vector<float> &table, 
 // The merge path's staging stream (merge_stage_build's bytes) from the device CSR and the
 // plan's slice corners: 0 built, 1 declined as the host would, < 0 on a HIP error (err).
 int devbuild_merge_stage(sm_matrix *m, hipStream_t s, hipError_t &err);
-// Layout decisions and host builders (layouts.cpp), which the constructors of capi.cpp end in.
+// Layout decisions and host builders (layouts.cpp), which the constructors of create.cpp end in.
 // resolve_opts: the caller's sm_build_opts with defaults for what its struct_size leaves out
 // and, in -DSM_DEV builds only, the SM_* development variables on top.  check_opts: the
 // options' ranges and exclusions (`table_ok`: the constructor builds a table matrix, the only
@@ -413,8 +413,11 @@ sm_status alloc_csr(sm_matrix *m);
 // Device CSR: `m` holds its sizes, options and the CSR arrays (alloc_csr) filled on `s`;
 // validates them by a kernel, plans, and builds the layouts on the device or the host as the
 // options ask; synchronises `s`.  `exact_sell`: also the unsegmented sliced ELL where
-// want_exact_sell asks for it (the host constructors' last step).
-sm_status finish_from_host_csr(sm_matrix *m, const int32_t *rp, const int32_t *col, const float *val);
+// want_exact_sell asks for it (the host constructors' last step).  A table_updatable matrix's
+// host builders take the matrix's own ids and table: the host tail is given them (`ids`, `table`),
+// the device tail downloads m->d_tab_ids and m->d_tab itself.
+sm_status finish_from_host_csr(sm_matrix *m, const int32_t *rp, const int32_t *col, const float *val,
+                               const uint8_t *ids = nullptr, const float *table = nullptr);
 sm_status finish_from_device_csr(sm_matrix *m, hipStream_t s, bool exact_sell);
 // The reference's stream the matrix holds on the host, on the device (native.hip).
 sm_status upload_native(sm_matrix *m);
@@ -612,8 +615,8 @@ struct sm_matrix {
     float *d_tab_partials = nullptr;
     int64_t tab_chunks = 0;
     mutable smamd::Turn table_turn;
-    // While a table_updatable matrix is being built: the host copies the layout builders take
-    // their ids and table from (owned by the constructor; null afterwards).
+    // While a table_updatable matrix's host builders run: the host copies they take their ids and
+    // table from (set and cleared by layouts.cpp's build_host_layouts alone; null otherwise).
     const uint8_t *build_ids = nullptr;
     const float *build_table = nullptr;
     std::vector<uint8_t> pos, val;

@@ -137,6 +137,17 @@ class SparseMatrix:
         return self._dims_cache
 
     # ---- construction -----------------------------------------------------
+    @classmethod
+    def _created(cls, device: int, fn, head, opts: Optional[dict], tail, name: str) -> "SparseMatrix":
+        """The shared end of the constructors that take sm_build_opts: a new matrix on `device`
+        from the C function ``fn(*head, &opts, *tail, &handle)``, the status checked under `name`."""
+        x = cls(device=device)
+        o = _lib.build_opts(**(opts or {}))
+        h = C.c_void_p()
+        check(fn(*head, C.byref(o), *tail, C.byref(h)), name)
+        x._h = h
+        return x
+
     def CopyForm(self, density_matrix, rows: int, cols: int, stride: int, vals,
                  val_table_size: int, trans: int = SblasNoTrans) -> None:
         """sparse-matrix.cc:20-99: encode a rows x stride uint8 id matrix with a float table."""
@@ -187,28 +198,22 @@ class SparseMatrix:
 
         `opts` (optional) forces the SpMV layout, e.g. ``{"layout": "exact"}`` or
         ``{"layout": "cband", "band_slabs": 1}`` -- the fields of sm_build_opts."""
-        self = cls(device=device)
+        L = _lib.load()
         n_rows = int(row_ptr.shape[0]) - 1
         nnz = int(col_idx.shape[0])
-        h = C.c_void_p()
-        o = _lib.build_opts(**(opts or {}))
         if _is_device(row_ptr):
             import torch
             assert row_ptr.dtype == torch.int32 and col_idx.dtype == torch.int32
             assert val.dtype == torch.float32
             rp, ci, va = row_ptr.contiguous(), col_idx.contiguous(), val.contiguous()
-            st = self._L.sm_create_from_csr_device_ex(n_rows, n_cols, nnz, _ptr(rp), _ptr(ci),
-                                                      _ptr(va), device, _stream_of(rp, stream),
-                                                      C.byref(o), C.byref(h))
-        else:
-            rp = np.ascontiguousarray(row_ptr, np.int32)
-            ci = np.ascontiguousarray(col_idx, np.int32)
-            va = np.ascontiguousarray(val, np.float32)
-            st = self._L.sm_create_from_csr_ex(n_rows, n_cols, nnz, _ptr(rp), _ptr(ci), _ptr(va),
-                                               device, C.byref(o), C.byref(h))
-        check(st, "from_csr")
-        self._h = h
-        return self
+            return cls._created(device, L.sm_create_from_csr_device_ex,
+                                (n_rows, n_cols, nnz, _ptr(rp), _ptr(ci), _ptr(va), device, _stream_of(rp, stream)),
+                                opts, (), "from_csr")
+        rp = np.ascontiguousarray(row_ptr, np.int32)
+        ci = np.ascontiguousarray(col_idx, np.int32)
+        va = np.ascontiguousarray(val, np.float32)
+        return cls._created(device, L.sm_create_from_csr_ex, (n_rows, n_cols, nnz, _ptr(rp), _ptr(ci), _ptr(va), device),
+                            opts, (), "from_csr")
 
     @classmethod
     def from_dense(cls, W, keep=None, per_row=None, threshold=None, opts: Optional[dict] = None,
@@ -242,14 +247,9 @@ class SparseMatrix:
         ld = int(W.stride(0)) if n_rows > 1 and W.numel() else n_cols   # an empty tensor's strides say nothing
         if ld < n_cols:
             raise ValueError(f"W has stride(0) = {ld} < {n_cols} columns (an expanded view?): use W.contiguous()")
-        self = cls(device=W.device.index)
-        o = _lib.build_opts(**(opts or {}))
-        h = C.c_void_p()
-        st = self._L.sm_create_from_dense_device(_ptr(W) if W.numel() else 0, n_rows, n_cols, ld, mode, count, thr,
-                                                 self.device, _stream_of(W, stream), C.byref(o), C.byref(h))
-        check(st, "from_dense")
-        self._h = h
-        return self
+        return cls._created(W.device.index, _lib.load().sm_create_from_dense_device,
+                            (_ptr(W) if W.numel() else 0, n_rows, n_cols, ld, mode, count, thr, W.device.index,
+                             _stream_of(W, stream)), opts, (), "from_dense")
 
     @classmethod
     def from_csr_ids(cls, row_ptr, col_idx, ids, table, n_cols: int, device: int = 0,
@@ -263,7 +263,6 @@ class SparseMatrix:
         Torch device tensors (all four) go to from_csr_ids_device on the current torch stream."""
         if any(_is_device(a) for a in (row_ptr, col_idx, ids, table)):
             return cls.from_csr_ids_device(row_ptr, col_idx, ids, table, n_cols, device=device, opts=opts)
-        self = cls(device=device)
         rp = np.ascontiguousarray(row_ptr, np.int32)
         ci = np.ascontiguousarray(col_idx, np.int32)
         idv = np.ascontiguousarray(ids, np.uint8).reshape(-1)
@@ -272,13 +271,9 @@ class SparseMatrix:
             raise ValueError(f"ids has {idv.size} elements, col_idx {ci.size}")
         if tb.size > 255 or (ci.size > 0 and tb.size < 1):
             raise ValueError(f"table must hold 1..255 values, got {tb.size}")
-        h = C.c_void_p()
-        o = _lib.build_opts(**(opts or {}))
-        st = self._L.sm_create_from_csr_ids(int(rp.shape[0]) - 1, n_cols, int(ci.size), _ptr(rp), _ptr(ci),
-                                            _ptr(idv), _ptr(tb), int(tb.size), device, C.byref(o), C.byref(h))
-        check(st, "from_csr_ids")
-        self._h = h
-        return self
+        return cls._created(device, _lib.load().sm_create_from_csr_ids,
+                            (int(rp.shape[0]) - 1, n_cols, int(ci.size), _ptr(rp), _ptr(ci), _ptr(idv), _ptr(tb),
+                             int(tb.size), device), opts, (), "from_csr_ids")
 
     @classmethod
     def from_csr_ids_device(cls, row_ptr, col_idx, ids, table, n_cols: int, device: int = 0,
@@ -305,15 +300,9 @@ class SparseMatrix:
             raise ValueError(f"ids has {idv.numel()} elements, col_idx {ci.numel()}")
         if tb.numel() > 255 or (ci.numel() > 0 and tb.numel() < 1):
             raise ValueError(f"table must hold 1..255 values, got {tb.numel()}")
-        self = cls(device=device)
-        h = C.c_void_p()
-        o = _lib.build_opts(**(opts or {}))
-        st = self._L.sm_create_from_csr_ids_device(int(rp.numel()) - 1, n_cols, int(ci.numel()), _ptr(rp), _ptr(ci),
-                                                   _ptr(idv), _ptr(tb), int(tb.numel()), device,
-                                                   _stream_of(rp, stream), C.byref(o), C.byref(h))
-        check(st, "from_csr_ids_device")
-        self._h = h
-        return self
+        return cls._created(device, _lib.load().sm_create_from_csr_ids_device,
+                            (int(rp.numel()) - 1, n_cols, int(ci.numel()), _ptr(rp), _ptr(ci), _ptr(idv), _ptr(tb),
+                             int(tb.numel()), device, _stream_of(rp, stream)), opts, (), "from_csr_ids_device")
 
     # ---- the transposed matrix ---------------------------------------------
     def transposed(self, opts: Optional[dict] = None, stream=None) -> "SparseMatrix":
@@ -324,17 +313,12 @@ class SparseMatrix:
         from the same index with the other `trans` (without the reference stream:
         build_ref_stream adds it).  Synchronises `stream` (None: the current torch stream)."""
         h0 = self._require()
-        t = SparseMatrix(device=self.device)
         if self._updatable():   # the companion of an updatable matrix follows its updates
             opts = dict(opts or {}, updatable=1)
         if self._table_updatable():
             opts = dict(opts or {}, table_updatable=1)
-        o = _lib.build_opts(**(opts or {}))
-        h = C.c_void_p()
-        st = self._L.sm_create_transpose(h0, C.byref(o), _stream_of(self, stream), C.byref(h))
-        check(st, "transposed")
-        t._h = h
-        return t
+        return SparseMatrix._created(self.device, self._L.sm_create_transpose, (h0,), opts,
+                                     (_stream_of(self, stream),), "transposed")
 
     @property
     def T(self) -> "SparseMatrix":
@@ -795,14 +779,8 @@ class SparseMatrix:
         table_size, iters = int(table_size), int(iters)
         if init is not None and self._codebook_operand(init, "init") != table_size:
             raise ValueError(f"init must hold table_size = {table_size} elements")
-        q = SparseMatrix(device=self.device)
-        o = _lib.build_opts(**(opts or {}))
-        h = C.c_void_p()
-        st = self._L.sm_create_quantized(h0, table_size, iters, _ptr(init), C.byref(o), _stream_of(self, stream),
-                                         C.byref(h))
-        check(st, "quantized")
-        q._h = h
-        return q
+        return SparseMatrix._created(self.device, self._L.sm_create_quantized, (h0, table_size, iters, _ptr(init)), opts,
+                                     (_stream_of(self, stream),), "quantized")
 
     # ---- pruning the stored terms by magnitude: mask, compact, rebuild ------------------------
     @staticmethod
@@ -849,13 +827,8 @@ class SparseMatrix:
             raise ValueError(f"keep must be a unit-stride 1-D tensor of nnz = {nnz} elements")
         if keep.device.index != self.device:
             raise ValueError("keep must be on the matrix's device")
-        p = SparseMatrix(device=self.device)
-        o = _lib.build_opts(**(opts or {}))
-        h = C.c_void_p()
-        st = self._L.sm_create_masked(h0, _ptr(keep) if nnz else 0, C.byref(o), _stream_of(self, stream), C.byref(h))
-        check(st, "masked")
-        p._h = h
-        return p
+        return SparseMatrix._created(self.device, self._L.sm_create_masked, (h0, _ptr(keep) if nnz else 0), opts,
+                                     (_stream_of(self, stream),), "masked")
 
     def pruned(self, keep=None, per_row=None, threshold=None, opts: Optional[dict] = None,
                stream=None) -> "SparseMatrix":
@@ -863,13 +836,8 @@ class SparseMatrix:
         ``P = M.pruned(keep=M.nnz // 2, opts={"updatable": 1})``.  Arguments as for those two."""
         h0 = self._require()
         mode, count, thr = self._prune_args(keep, per_row, threshold)
-        p = SparseMatrix(device=self.device)
-        o = _lib.build_opts(**(opts or {}))
-        h = C.c_void_p()
-        st = self._L.sm_create_pruned(h0, mode, count, thr, C.byref(o), _stream_of(self, stream), C.byref(h))
-        check(st, "pruned")
-        p._h = h
-        return p
+        return SparseMatrix._created(self.device, self._L.sm_create_pruned, (h0, mode, count, thr), opts,
+                                     (_stream_of(self, stream),), "pruned")
 
     def source_terms_device(self, stream=None):
         """For a matrix made by masked / pruned (or transposed with ``opts={"updatable": 1}``):
@@ -899,13 +867,8 @@ class SparseMatrix:
         if not isinstance(other, SparseMatrix):
             raise TypeError("other must be a SparseMatrix")
         h1 = other._require()
-        c = SparseMatrix(device=self.device)
-        o = _lib.build_opts(**(opts or {}))
-        h = C.c_void_p()
-        st = self._L.sm_create_sum(h0, float(alpha), h1, float(beta), C.byref(o), _stream_of(self, stream), C.byref(h))
-        check(st, "sum")
-        c._h = h
-        return c
+        return SparseMatrix._created(self.device, self._L.sm_create_sum, (h0, float(alpha), h1, float(beta)), opts,
+                                     (_stream_of(self, stream),), "sum")
 
     def sum_terms_device(self, stream=None):
         """For a matrix made by sum: ``(terms_a, terms_b)``, two new int32 tensors of nnz elements on

@@ -340,3 +340,48 @@ def test_device_csr_validation_flags(sm):
     for r, c in ((rp, bad_col), (rp, neg_col), (bad_first, ci), (bad_last, ci), (bad_order, ci)):
         with pytest.raises(sm.SparseMatrixError):
             build(r, c)
+
+
+def test_a_failed_constructor_leaves_nothing_behind(sm):
+    """Three device-side constructors refused for what their arguments hold (a column index equal
+    to n_cols, an id equal to T, a stored NaN), on a side stream: each returns its documented
+    status and no handle, the stream then synchronises clean (sm_stream_sync reads the last HIP
+    error), and the same constructor given valid arrays works on the same stream."""
+    import ctypes as C
+
+    from sparsematrix_amd import _lib
+    torch = torch_dev()
+    L = _lib.load()
+    INVALID_MATRIX = _lib.SM_ERR_INVALID_MATRIX
+    rp, ci = np.array([0, 2, 3], np.int32), np.array([0, 2, 1], np.int32)   # 2 x 3, 3 terms
+    table, ids = np.array([0.5, -1.25], np.float32), np.array([0, 1, 1], np.uint8)
+    va = table[ids]
+    x, y0 = np.array([1.5, -2.0, 0.25], np.float32), np.array([0.75, -3.0], np.float32)
+    want = oracle.csr_spmv(rp, ci, va, x, y0, 1.3, 0.7)
+    dev = lambda a: torch.from_numpy(a).cuda()
+    side = torch.cuda.Stream()
+    s = side.cuda_stream
+
+    def refused(call):
+        h, o = C.c_void_p(1), _lib.build_opts()
+        assert call(C.byref(o), C.byref(h)) == INVALID_MATRIX, L.sm_last_error()
+        assert not h.value, "a handle came back from a failed constructor"
+        assert L.sm_stream_sync(s) == 0, L.sm_last_error()
+
+    def multiplies(M):
+        y = dev(y0)
+        M.spmv(dev(x), y, 1.3, 0.7, algo="parity")
+        assert np.array_equal(bits(to_host(y)), bits(want))
+
+    with torch.cuda.stream(side):
+        d_rp, d_ci, d_va, d_ids, d_table = dev(rp), dev(ci), dev(va), dev(ids), dev(table)
+        bad_ci, bad_ids = dev(np.array([0, 3, 1], np.int32)), dev(np.array([0, 2, 1], np.uint8))
+        p = lambda t: t.data_ptr()
+        refused(lambda o, h: L.sm_create_from_csr_device_ex(2, 3, 3, p(d_rp), p(bad_ci), p(d_va), 0, s, o, h))
+        multiplies(sm.SparseMatrix.from_csr(d_rp, d_ci, d_va, 3))
+        refused(lambda o, h: L.sm_create_from_csr_ids_device(2, 3, 3, p(d_rp), p(d_ci), p(bad_ids), p(d_table), 2, 0, s,
+                                                             o, h))
+        multiplies(sm.SparseMatrix.from_csr_ids_device(d_rp, d_ci, d_ids, d_table, 3))
+        holds_nan = sm.SparseMatrix.from_csr(rp, ci, np.array([0.5, np.nan, -1.25], np.float32), 3)
+        refused(lambda o, h: L.sm_create_quantized(holds_nan._h, 2, 0, None, o, s, h))
+        multiplies(sm.SparseMatrix.from_csr(rp, ci, va, 3).quantized(table_size=2, iters=0, init=d_table))

@@ -483,3 +483,53 @@ def test_refusals(sm):
     bad = ids.copy()
     bad[17] = T
     assert _status(lambda: sm.SparseMatrix.from_csr_ids(rp, ci, bad, table, 257)) == INVALID_MATRIX
+
+
+# ------------------------------------------------------ derived table matrices on a side stream
+@pytest.mark.parametrize("opts", [{}, {"table_updatable": 1}], ids=["default", "table_updatable"])
+def test_derived_table_matrices_on_a_side_stream(sm, opts):
+    """transposed, masked and quantized of a table matrix, made on a non-blocking stream, hold
+    the source's table bit for bit and the restated ids, and multiply as the oracle does.
+
+    This guards the stream ordering of the table hand-on: the new matrix's table is zeroed on the
+    default stream and filled on the caller's, and nothing but the hand-on orders the two on a
+    stream such as this one.  A missing order is a race, so this test cannot be made to fail
+    reliably on a library that lacks it, and it is not looped to try."""
+    import oracle
+    import prune_ref
+    import quantize_ref
+    torch = torch_dev()
+    oracle.build()
+    n_rows, n_cols, T = 5, 7, 3
+    rp = np.array([0, 2, 4, 5, 7, 9], np.int32)
+    ci = np.array([0, 3, 1, 3, 6, 2, 5, 0, 4], np.int32)
+    ids = np.array([0, 1, 2, 0, 1, 2, 0, 1, 2], np.uint8)
+    table = np.array([0.5, -1.25, 3.0], np.float32)
+    va = table[ids]
+    keep = np.ones(ci.size, np.uint8)
+    keep[4] = 0
+    # the restatements: a stable sort by column; the compaction; the assignment rule
+    order = np.argsort(ci, kind="stable")
+    t_rp = np.concatenate([[0], np.cumsum(np.bincount(ci, minlength=n_cols))]).astype(np.int32)
+    t_ci = np.repeat(np.arange(n_rows, dtype=np.int32), np.diff(rp))[order]
+    m_rp, m_ci, _, m_ids, _ = prune_ref.compact(rp, ci, va, keep, ids)
+    want = {"transposed": (t_rp, t_ci, ids[order], n_rows),
+            "masked": (m_rp, m_ci, m_ids, n_cols),
+            "quantized": (rp, ci, quantize_ref.assign(va, table), n_cols)}
+    M = sm.SparseMatrix.from_csr_ids(rp, ci, ids, table, n_cols, opts=opts)
+    rng = np.random.default_rng(31)
+    with torch.cuda.stream(torch.cuda.Stream()):
+        made = {"transposed": M.transposed(opts=opts),
+                "masked": M.masked(to_dev(keep), opts=opts),
+                "quantized": M.quantized(table_size=T, iters=0, init=M.table_device(), opts=opts)}
+        for name, D in made.items():
+            w_rp, w_ci, w_ids, w_cols = want[name]
+            assert np.array_equal(bits(to_host(D.table_device())), bits(table)), name + ": table"
+            assert np.array_equal(to_host(D.term_ids_device()), w_ids), name + ": ids"
+            assert D.info()["table_size"] == T and D.info()["table_updatable"] == opts.get("table_updatable", 0), name
+            x = rng.uniform(-1, 1, w_cols).astype(np.float32)
+            y0 = rng.uniform(-1, 1, w_rp.size - 1).astype(np.float32)
+            y = to_dev(y0)
+            D.spmv(to_dev(x), y, 1.3, 0.7, algo="parity")
+            assert np.array_equal(bits(to_host(y)), bits(oracle.csr_spmv(w_rp, w_ci, table[w_ids], x, y0, 1.3, 0.7))), \
+                name + ": spmv"
