@@ -4,13 +4,15 @@
 // ascending column order across the tile's bands (bands ascend, ranks ascend in a
 // band), ranks are the term's index in its segment, a segment never spans two
 // chunks, columns stay inside the band's 8192-column window, bands ascend and never
-// overlap, and padding decodes as dummies with value 0.
+// overlap, and padding decodes as dummies with value 0.  The same checks run over the grid
+// of small shapes (small_grid.h, check_grid).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <random>
 #include <vector>
 
+#include "small_grid.h"
 #include "xband.h"
 
 using namespace smamd;
@@ -30,9 +32,10 @@ static int check_layout(const std::vector<int32_t> &rp, const std::vector<int32_
     const bool ok = band2_build(rp.data(), col.data(), val.data(), n_rows, n_cols, slabs, h, nullptr, geom, permille);
     const uint32_t kDummy = geom.dummy_word();
     const int kCol = geom.col_bits;
+    const int64_t bw = (int64_t)128 * geom.chunks();   // words per band: 4096 but for dma3's 30 chunks
     if (ok != expect_ok) { printf("FAIL build=%d expected %d\n", ok, expect_ok); return 1; }
     if (!ok) return 0;
-    if ((int64_t)h.band_clo.size() != h.n_bands || (int64_t)h.ent.size() != h.n_bands * 4096) {
+    if ((int64_t)h.band_clo.size() != h.n_bands || (int64_t)h.ent.size() != h.n_bands * bw) {
         printf("FAIL sizes\n"); return 1; }
     std::vector<std::vector<std::pair<int32_t, float>>> got(n_rows);
     int64_t terms = 0;
@@ -46,11 +49,11 @@ static int check_layout(const std::vector<int32_t> &rp, const std::vector<int32_
             const int64_t clo = h.band_clo[g];
             if (clo % 4) { printf("FAIL clo alignment\n"); return 1; }
             int64_t lo_col = INT64_MAX, hi_col = -1;
-            for (int c = 0; c < kB2Chunks; c++) {
+            for (int c = 0; c < geom.chunks(); c++) {
                 const int wave = c >> 1, k = c & 1;
                 std::vector<int> rows_seen;
                 for (int l = 0; l < 64; l++) {
-                    const uint32_t *e = &h.ent[(size_t)g * 4096 + (size_t)(wave * 64 + l) * 4];
+                    const uint32_t *e = &h.ent[(size_t)g * bw + (size_t)(wave * 64 + l) * 4];
                     const uint32_t w = e[k] ^ kDummy;
                     const uint32_t rank = (w >> kCol) & kB2DummyRank;
                     float v;
@@ -67,7 +70,7 @@ static int check_layout(const std::vector<int32_t> &rp, const std::vector<int32_
                     if (cc - clo >= geom.window || cc < c0 || cc >= c1) { printf("FAIL window\n"); return 1; }
                     if ((int)rank != (int)std::count(rows_seen.begin(), rows_seen.end(), (int)rl)) {
                         printf("FAIL rank\n"); return 1; }
-                    if (rank > 0 && (l == 0 || ((h.ent[(size_t)g * 4096 + (size_t)(wave * 64 + l - 1) * 4 + k] ^
+                    if (rank > 0 && (l == 0 || ((h.ent[(size_t)g * bw + (size_t)(wave * 64 + l - 1) * 4 + k] ^
                                                  kDummy) >> (kCol + kB2RankBits)) != rl)) {
                         printf("FAIL segment not on consecutive lanes\n"); return 1; }
                     rows_seen.push_back((int)rl);
@@ -203,8 +206,43 @@ static int check_random(int64_t n_rows, int64_t n_cols, int per_row, unsigned se
     return bad;
 }
 
-int main() {
+// The grid of small shapes (small_grid.h): both encodings, the kernel's two geometries (dma3
+// and wide, as sm_build_opts.band_tall 0 and 6 choose them) and 1, 2 and 3 slabs, with the checks
+// above.  Whether the builder took the case is printed; a slab count b2_slabs did not give fails.
+static int check_grid() {
     int bad = 0;
+    small_grid::for_each([&](small_grid::Shape s, int p, const small_grid::Csr &m) {
+        for (int slabs : {1, 2, 3}) {
+            const struct { const char *name; B2Geom geom; bool cb; } forms[] = {
+                {"band2-tall0", kB2Dma3B2, false}, {"band2-tall6", kB2Wide, false},
+                {"cband-tall0", kB2Dma3Cb, true}, {"cband-tall6", kB2Wide, true}};
+            for (const auto &f : forms) {
+                std::vector<float> table;
+                std::vector<uint8_t> ids;
+                if (f.cb && !codebook_ids(m.cb.data(), (int64_t)m.cb.size(), table, ids)) { printf("FAIL grid codebook\n"); bad++; continue; }
+                Band2Host h;
+                const bool ok = band2_build(m.rp.data(), m.col.data(), m.cb.data(), m.n_rows, m.n_cols, slabs, h,
+                                            f.cb ? ids.data() : nullptr, f.geom);
+                char name[64];
+                snprintf(name, sizeof name, "%s-slabs%d", f.name, slabs);
+                small_grid::report(name, s, p, ok);
+                if (!ok) continue;
+                const int64_t sc = (((m.n_cols + slabs - 1) / slabs) + 255) & ~(int64_t)255;
+                if (h.n_slabs != (m.n_cols + sc - 1) / sc || h.slab_cols != sc || h.n_blocks != 1 ||
+                    h.block_rows != m.n_rows || h.real_terms != (int64_t)m.col.size()) {
+                    printf("FAIL grid geometry %s\n", name); bad++; continue; }
+                const int b = f.cb ? check_layout_cb(m.rp, m.col, m.cb, m.n_rows, m.n_cols, slabs, f.geom)
+                                   : check_layout(m.rp, m.col, m.cb, m.n_rows, m.n_cols, slabs, true, f.geom);
+                if (b) printf("  ... at grid %s %dx%d %s\n", name, s.rows, s.cols, small_grid::kPatterns[p]);
+                bad += b;
+            }
+        }
+    });
+    return bad;
+}
+
+int main() {
+    int bad = check_grid();
     for (int slabs : {1, 4, 16}) {
         bad += check_random(20011, 300001, 16, 1, slabs, true);
         bad += check_random(3001, 70001, 40, 2, slabs, true);

@@ -14,6 +14,7 @@
 
 #include "ccsell.h"
 #include "sell.h"
+#include "small_grid.h"
 
 using namespace smamd;
 
@@ -108,6 +109,23 @@ static int random_case(int64_t n_rows, int64_t n_cols, int per_row, unsigned see
 
 int main() {
     int bad = 0;
+    // The grid of small shapes (small_grid.h) with 256-column chunks (the smallest chunk_log2 the
+    // options take), codebook and plain form, sorted by length and in row order; whether the
+    // builder took the case is printed.
+    small_grid::for_each([&](small_grid::Shape s, int p, const small_grid::Csr &m) {
+        for (bool cb : {true, false}) {
+            std::vector<uint8_t> ids(m.col.size(), 0);
+            CcsellHost probe;
+            const bool ok = ccsell_build(m.rp.data(), m.col.data(), m.cb.data(), cb ? ids.data() : nullptr, m.n_rows,
+                                         m.n_cols, 8, probe);
+            small_grid::report(cb ? "sell-ccsell" : "ccsell-plain", s, p, ok && probe.n_slices > 0);
+            if (!ok) continue;
+            const int b = check(m.rp, m.col, m.cb, m.n_rows, m.n_cols, 8, cb) +
+                          check(m.rp, m.col, cb ? m.cb : m.plain, m.n_rows, m.n_cols, 8, cb, false);
+            if (b) printf("  ... at grid ccsell %dx%d %s\n", s.rows, s.cols, small_grid::kPatterns[p]);
+            bad += b;
+        }
+    });
     for (bool cb : {true, false}) {
         bad += random_case(20000, 1 << 20, 16, 1, 16, cb);
         bad += random_case(5000, 300001, 40, 2, 12, cb);

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "gcb.h"
+#include "small_grid.h"
 
 using namespace smamd;
 
@@ -95,6 +96,26 @@ static int check(const std::vector<int32_t> &rp, const std::vector<int32_t> &col
 int main() {
     std::mt19937_64 rng(42);
     int fails = 0;
+    // The grid of small shapes (small_grid.h) as a forced gcb layout is built (16K-row tiles, the
+    // widest window), 1 and 3 slabs, with check()'s decoding; whether the builder took the case
+    // is printed.
+    small_grid::for_each([&](small_grid::Shape s, int p, const small_grid::Csr &m) {
+        for (int slabs : {1, 3}) {
+            GcbHost probe;
+            const bool ok = gcb_build(m.rp.data(), m.col.data(), m.plain.data(), m.n_rows, m.n_cols, 14, slabs,
+                                      kGcbMaxWindow, probe);
+            char name[32];
+            snprintf(name, sizeof name, "gcb-slabs%d", slabs);
+            small_grid::report(name, s, p, ok);
+            if (!ok) continue;
+            const int64_t sc = (((m.n_cols + slabs - 1) / slabs) + 255) & ~(int64_t)255;
+            if (probe.n_slabs != (m.n_cols + sc - 1) / sc || probe.slab_cols != sc || probe.n_blocks != 1 ||
+                probe.block_rows != m.n_rows) { printf("FAIL grid geometry\n"); fails++; continue; }
+            const int b = check(m.rp, m.col, m.plain, m.n_rows, m.n_cols, 14, slabs, kGcbMaxWindow);
+            if (b) printf("  ... at grid %s %dx%d %s\n", name, s.rows, s.cols, small_grid::kPatterns[p]);
+            fails += b;
+        }
+    });
     struct Case { int64_t rows, cols; int per, rows_log2, slabs; int32_t window; };
     for (const Case &c : {Case{20000, 3000001, 16, 15, 1, 1 << 18}, Case{20000, 3000001, 16, 14, 3, 1 << 18},
                           Case{9000, 70001, 40, 14, 1, 4096}, Case{5000, 1000, 5, 14, 2, 1 << 18},

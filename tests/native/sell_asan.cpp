@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sell.h"
+#include "small_grid.h"
 
 using namespace smamd;
 
@@ -102,6 +103,26 @@ static int check(const std::vector<int32_t> &rp, const std::vector<int32_t> &col
 
 int main() {
     int bad = 0;
+    // The grid of small shapes (small_grid.h): the codebook and the plain form at the default cap,
+    // the codebook form cut at 64 terms (long-row segments), and caps of 1 and 8 with windows.
+    // The builder declines nothing; a case without a slice would leave the layout unbuilt.
+    small_grid::for_each([&](small_grid::Shape s, int p, const small_grid::Csr &m) {
+        const struct { const char *name; int32_t max_len; bool cb; } forms[] = {
+            {"sell-codebook", kSellMaxLen, true}, {"sell-plain", kSellMaxLen, false}, {"sell-long-rows", 64, true}};
+        int b = 0;
+        for (const auto &f : forms) {
+            SellHost probe;
+            sell_build(m.rp.data(), m.col.data(), m.small.data(), m.n_rows, f.max_len, probe);
+            small_grid::report(f.name, s, p, probe.n_slices > 0);
+            b += check(m.rp, m.col, m.small, m.n_rows, f.max_len, 0, 1, f.cb);
+        }
+        for (int32_t mx : {1, 8}) {
+            b += check(m.rp, m.col, m.small, m.n_rows, mx);
+            b += check(m.rp, m.col, m.small, m.n_rows, mx, 64, 3, true);
+        }
+        if (b) printf("  ... at grid sell %dx%d %s\n", s.rows, s.cols, small_grid::kPatterns[p]);
+        bad += b;
+    });
     std::mt19937 rng(5);
     for (int64_t n_rows : {1, 63, 64, 65, 1000, 70001}) {
         for (int skew = 0; skew < 2; skew++) {

@@ -13,6 +13,7 @@
 #include <random>
 #include <vector>
 
+#include "small_grid.h"
 #include "xband.h"
 
 using namespace smamd;
@@ -141,9 +142,23 @@ int main() {
     const XbBits blocked = xb_bits(kXbBlockedBandLog2, kXbBlockedRowsLog2);
     int bad = 0;
     const XbBits gather = xb_bits(kXbGatherBandLog2, kXbGatherRowsLog2);
-    const struct { XbBits bits; int waves; bool col_order; } kinds[] = {
-        {exact, kXbThreads / 64, false}, {blocked, kXbComputeWaves, false},
-        {gather, kXbThreads / 64, true}};
+    const struct { XbBits bits; int waves; bool col_order; const char *name; } kinds[] = {
+        {exact, kXbThreads / 64, false, "exact"}, {blocked, kXbComputeWaves, false, "blocked"},
+        {gather, kXbThreads / 64, true, "gather"}};
+    // The grid of small shapes (small_grid.h) in the three bit layouts, with verify()'s checks;
+    // whether the builder took the case is printed.
+    for (const auto &k : kinds)
+        small_grid::for_each([&](small_grid::Shape s, int p, const small_grid::Csr &m) {
+            XbandHost probe;
+            const bool ok = xband_build(m.rp.data(), m.col.data(), m.cb.data(), m.n_rows, m.n_cols, k.bits, k.waves,
+                                        probe, k.col_order);
+            small_grid::report(k.name, s, p, ok);
+            if (ok && (probe.n_bands != 1 || probe.n_blocks * (int64_t)probe.block_rows < m.n_rows)) {
+                printf("FAIL grid geometry\n"); bad++; }
+            const int b = verify(k.bits, k.waves, m.rp, m.col, m.cb, m.n_cols, ok, k.col_order);
+            if (b) printf("  ... at grid %s %dx%d %s\n", k.name, s.rows, s.cols, small_grid::kPatterns[p]);
+            bad += b;
+        });
     for (const auto &k : kinds) {
         const bool co = k.col_order;
         bad += check(k.bits, k.waves, 200003, 300001, 16, 1, true, co);

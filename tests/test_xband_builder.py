@@ -1,7 +1,9 @@
 """Host logic of the column-band layout builder (sparsematrix_amd/csrc/xband.cpp),
 no GPU: tests/native/xband_asan.cpp is compiled with AddressSanitizer and run.
 It rebuilds every row from the layout (both the exact and the blocked bit layout)
-and checks order, ranks, register capacity and the dummy encoding."""
+and checks order, ranks, register capacity and the dummy encoding.  The builder programs also
+run the grid of small cases (tests/small_shapes.py) and print which cases they decline:
+_check_grid holds that printout against the DECLINES table of tests/test_gpu_small_shapes.py."""
 import os
 import shutil
 import subprocess
@@ -9,6 +11,28 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _check_grid(stdout, layouts):
+    """The programs' report on the grid of small cases (tests/small_shapes.py, restated in
+    tests/native/small_grid.h): every (layout, shape, pattern) once, the declined ones exactly
+    those of DECLINES (tests/test_gpu_small_shapes.py), and no layout declined on every pattern of
+    more than half of the shapes."""
+    import small_shapes as ss
+    from test_gpu_small_shapes import DECLINES, HOST_BUILDER_LAYOUTS
+    seen = {}
+    for line in stdout.splitlines():
+        if line.startswith("grid "):
+            _, layout, shape, pattern, verdict = line.split()
+            key = (layout, tuple(int(v) for v in shape.split("x")), pattern)
+            assert key not in seen and verdict in ("built", "declined"), line
+            seen[key] = verdict == "declined"
+    assert set(layouts) <= set(HOST_BUILDER_LAYOUTS)
+    assert set(seen) >= {(n, s, p) for n in layouts for s, p in ss.GRID}
+    declined = {k for k, d in seen.items() if d and k[0] in layouts}
+    assert declined == {k for k in DECLINES if k[0] in layouts}, sorted(declined ^ {k for k in DECLINES if k[0] in layouts})
+    for n in layouts:
+        assert 2 * len(ss.declined_widely(declined, n)) <= len(ss.SHAPES), n
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
@@ -23,6 +47,7 @@ def test_xband_builder_under_asan(tmp_path):
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "xband_asan: ok" in r.stdout
+    _check_grid(r.stdout, ("exact", "blocked", "gather"))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
@@ -39,6 +64,7 @@ def test_band2_builder_under_asan(tmp_path):
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "band2_asan: ok" in r.stdout
+    _check_grid(r.stdout, [f"{k}-tall{t}-slabs{n}" for k in ("band2", "cband") for t in (0, 6) for n in (1, 2, 3)])
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
@@ -55,6 +81,7 @@ def test_sell_builder_under_asan(tmp_path):
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "sell_asan: ok" in r.stdout
+    _check_grid(r.stdout, ("sell-codebook", "sell-plain", "sell-long-rows"))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
@@ -71,6 +98,7 @@ def test_ccsell_builder_under_asan(tmp_path):
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "ccsell_asan: ok" in r.stdout
+    _check_grid(r.stdout, ("sell-ccsell",))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
@@ -123,6 +151,7 @@ def test_gcb_builder_under_asan(tmp_path):
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "gcb_asan: ok" in r.stdout
+    _check_grid(r.stdout, ("gcb-slabs1", "gcb-slabs3"))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
