@@ -16,12 +16,11 @@
 //   merge     the merge path's column-sorted staging stream (merge.cpp merge_stage_build): a
 //             stable radix sort of every slice's terms by (slice, column), then column << 8 |
 //             id and the term's offset in its slice.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
+#include "devprim.h"
 #include "merge.h"
 #include "sell.h"
 #include "sm_internal.h"
@@ -29,20 +28,9 @@
 namespace smamd {
 namespace {
 
-unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
-
-#define GS_LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
 __global__ __launch_bounds__(256) void bd_degree_kernel(int64_t nnz, const int32_t *__restrict__ col,
                                                         int32_t *__restrict__ deg) {
     GS_LOOP(e, nnz) atomicAdd(&deg[col[e]], 1);
-}
-
-__global__ __launch_bounds__(256) void bd_max_kernel(int64_t n, const int32_t *__restrict__ v, int32_t *__restrict__ out) {
-    int32_t mx = 0;
-    GS_LOOP(i, n) mx = max(mx, v[i]);
-    for (int d = 32; d >= 1; d >>= 1) mx = max(mx, __shfl_xor(mx, d, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, mx);
 }
 
 // key = dmax - degree (ascending key = descending degree), value = the column.
@@ -239,41 +227,6 @@ __global__ __launch_bounds__(256) void bd_mstage_kernel(int64_t n, const unsigne
     }
 }
 
-#define BD_TRY(x)                  \
-    do {                           \
-        const hipError_t e_ = (x); \
-        if (e_ != hipSuccess) {    \
-            err = e_;              \
-            return -5;             \
-        }                          \
-    } while (0)
-
-template <class K, class V>
-hipError_t sort_pairs(DevScratch &t, const K *k, K *ks, const V *v, V *vs, int64_t n, int end_bit, hipStream_t s) {
-    size_t bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k, ks, v, vs, (int)n, 0, end_bit, s);
-    if (e != hipSuccess) return e;
-    uint8_t *tmp = nullptr;
-    if ((e = t.alloc(&tmp, (int64_t)bytes)) != hipSuccess) return e;
-    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k, ks, v, vs, (int)n, 0, end_bit, s);
-}
-
-template <class T, class O>
-hipError_t excl_sum(DevScratch &t, const T *in, O *out, int64_t n, hipStream_t s) {
-    size_t bytes = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, s);
-    if (e != hipSuccess) return e;
-    uint8_t *tmp = nullptr;
-    if ((e = t.alloc(&tmp, (int64_t)bytes)) != hipSuccess) return e;
-    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (int)n, s);
-}
-
-int bits_for(uint32_t v) {
-    int b = 1;
-    while (b < 32 && (v >> b) != 0) ++b;
-    return b;
-}
-
 }  // namespace
 
 int devbuild_relabel(sm_matrix *m, bool check_skew, hipStream_t s, hipError_t &err) {
@@ -284,43 +237,43 @@ int devbuild_relabel(sm_matrix *m, bool check_skew, hipStream_t s, hipError_t &e
     int32_t *deg = nullptr, *dmx = nullptr, *idx = nullptr, *perm = nullptr;
     uint32_t *key = nullptr, *skey = nullptr;
     unsigned long long *hot = nullptr;
-    BD_TRY(t.alloc(&deg, nc));
-    BD_TRY(t.alloc(&dmx, 1));
-    BD_TRY(t.alloc(&hot, 1));
-    BD_TRY(hipMemsetAsync(deg, 0, (size_t)nc * 4, s));
-    BD_TRY(hipMemsetAsync(dmx, 0, 4, s));
-    BD_TRY(hipMemsetAsync(hot, 0, 8, s));
+    DEV_TRY(t.alloc(&deg, nc));
+    DEV_TRY(t.alloc(&dmx, 1));
+    DEV_TRY(t.alloc(&hot, 1));
+    DEV_TRY(hipMemsetAsync(deg, 0, (size_t)nc * 4, s));
+    DEV_TRY(hipMemsetAsync(dmx, 0, 4, s));
+    DEV_TRY(hipMemsetAsync(hot, 0, 8, s));
     hipLaunchKernelGGL(bd_degree_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, m->d_col, deg);
-    hipLaunchKernelGGL(bd_max_kernel, dim3(grid_of(nc)), dim3(256), 0, s, nc, deg, dmx);
-    BD_TRY(hipGetLastError());
+    hipLaunchKernelGGL(max_i32_kernel<>, dim3(grid_of(nc)), dim3(256), 0, s, nc, deg, dmx);
+    DEV_TRY(hipGetLastError());
     int32_t dmax = 0;
-    BD_TRY(hipMemcpyAsync(&dmax, dmx, 4, hipMemcpyDeviceToHost, s));
-    BD_TRY(hipStreamSynchronize(s));
-    BD_TRY(t.alloc(&key, nc));
-    BD_TRY(t.alloc(&skey, nc));
-    BD_TRY(t.alloc(&idx, nc));
-    BD_TRY(t.alloc(&perm, nc));
+    DEV_TRY(hipMemcpyAsync(&dmax, dmx, 4, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipStreamSynchronize(s));
+    DEV_TRY(t.alloc(&key, nc));
+    DEV_TRY(t.alloc(&skey, nc));
+    DEV_TRY(t.alloc(&idx, nc));
+    DEV_TRY(t.alloc(&perm, nc));
     hipLaunchKernelGGL(bd_colkey_kernel, dim3(grid_of(nc)), dim3(256), 0, s, nc, deg, dmax, key, idx);
-    BD_TRY(hipGetLastError());
-    BD_TRY(sort_pairs(t, key, skey, idx, perm, nc, bits_for((uint32_t)dmax), s));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(dev_sort_pairs(t, key, skey, idx, perm, nc, bits_for((uint32_t)dmax), s));
     int32_t *rank = nullptr;
-    BD_TRY(m->mem.alloc(&p.d_perm, nc + 4));
+    DEV_TRY(m->mem.alloc(&p.d_perm, nc + 4));
     rank = p.d_perm;
     hipLaunchKernelGGL(bd_rank_kernel, dim3(grid_of(nc)), dim3(256), 0, s, nc, perm, skey, dmax, nc / 16, rank, hot);
-    BD_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     unsigned long long hot_h = 0;
-    BD_TRY(hipMemcpyAsync(&hot_h, hot, 8, hipMemcpyDeviceToHost, s));
-    BD_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipMemcpyAsync(&hot_h, hot, 8, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipStreamSynchronize(s));
     if (check_skew && (double)hot_h < 0.4 * (double)nnz) {   // not skewed: no gain (upload_relabel)
         m->mem.release(p.d_perm);
         return 0;
     }
-    BD_TRY(m->mem.alloc(&p.d_rcol, nnz + kPadElems));
-    BD_TRY(m->mem.alloc(&p.d_xperm, nc + 4));
+    DEV_TRY(m->mem.alloc(&p.d_rcol, nnz + kPadElems));
+    DEV_TRY(m->mem.alloc(&p.d_xperm, nc + 4));
     hipLaunchKernelGGL(bd_remap_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, m->d_col, rank, p.d_rcol);
-    BD_TRY(hipGetLastError());
-    BD_TRY(hipMemsetAsync(p.d_rcol + nnz, 0, kPadElems * sizeof(int32_t), s));
-    BD_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipMemsetAsync(p.d_rcol + nnz, 0, kPadElems * sizeof(int32_t), s));
+    DEV_TRY(hipStreamSynchronize(s));
     p.n_relabel = nc;
     return 0;
 }
@@ -333,27 +286,27 @@ int devbuild_codebook(const float *d_val, int64_t n, std::vector<float> &table, 
     DevScratch t;
     uint32_t *bits = nullptr, *bits_s = nullptr, *hb = nullptr;
     int32_t *idx = nullptr, *idx_s = nullptr, *nh = nullptr, *hi = nullptr;
-    BD_TRY(t.alloc(&bits, n));
-    BD_TRY(t.alloc(&bits_s, n));
-    BD_TRY(t.alloc(&idx, n));
-    BD_TRY(t.alloc(&idx_s, n));
-    BD_TRY(t.alloc(&nh, 1));
-    BD_TRY(t.alloc(&hb, 256));
-    BD_TRY(t.alloc(&hi, 256));
+    DEV_TRY(t.alloc(&bits, n));
+    DEV_TRY(t.alloc(&bits_s, n));
+    DEV_TRY(t.alloc(&idx, n));
+    DEV_TRY(t.alloc(&idx_s, n));
+    DEV_TRY(t.alloc(&nh, 1));
+    DEV_TRY(t.alloc(&hb, 256));
+    DEV_TRY(t.alloc(&hi, 256));
     hipLaunchKernelGGL(bd_bits_kernel, dim3(grid_of(n)), dim3(256), 0, s, n, d_val, bits, idx);
-    BD_TRY(hipGetLastError());
-    BD_TRY(sort_pairs(t, bits, bits_s, idx, idx_s, n, 32, s));
-    BD_TRY(hipMemsetAsync(nh, 0, 4, s));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(dev_sort_pairs(t, bits, bits_s, idx, idx_s, n, 32, s));
+    DEV_TRY(hipMemsetAsync(nh, 0, 4, s));
     hipLaunchKernelGGL(bd_heads_kernel, dim3(grid_of(n)), dim3(256), 0, s, n, bits_s, idx_s, nh, hb, hi);
-    BD_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     int32_t K = 0;
-    BD_TRY(hipMemcpyAsync(&K, nh, 4, hipMemcpyDeviceToHost, s));
-    BD_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipMemcpyAsync(&K, nh, 4, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipStreamSynchronize(s));
     if (K > 255) return 1;   // codebook_ids: at most kCbDummyId = 255 ids
     std::vector<uint32_t> hbits((size_t)K);
     std::vector<int32_t> hidx((size_t)K);
-    BD_TRY(hipMemcpy(hbits.data(), hb, (size_t)K * 4, hipMemcpyDeviceToHost));
-    BD_TRY(hipMemcpy(hidx.data(), hi, (size_t)K * 4, hipMemcpyDeviceToHost));
+    DEV_TRY(hipMemcpy(hbits.data(), hb, (size_t)K * 4, hipMemcpyDeviceToHost));
+    DEV_TRY(hipMemcpy(hidx.data(), hi, (size_t)K * 4, hipMemcpyDeviceToHost));
     std::vector<int32_t> ord((size_t)K);
     for (int32_t i = 0; i < K; i++) ord[(size_t)i] = i;
     std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t c) { return hidx[(size_t)a] < hidx[(size_t)c]; });
@@ -371,13 +324,13 @@ int devbuild_codebook(const float *d_val, int64_t n, std::vector<float> &table, 
     for (int32_t i = 0; i < K; i++) tb[(size_t)i] = book[(size_t)i].first, tid[(size_t)i] = book[(size_t)i].second;
     uint32_t *d_tb = nullptr;
     uint8_t *d_tid = nullptr;
-    BD_TRY(t.alloc(&d_tb, 256));
-    BD_TRY(t.alloc(&d_tid, 256));
-    BD_TRY(hipMemcpy(d_tb, tb.data(), (size_t)K * 4, hipMemcpyHostToDevice));
-    BD_TRY(hipMemcpy(d_tid, tid.data(), (size_t)K, hipMemcpyHostToDevice));
+    DEV_TRY(t.alloc(&d_tb, 256));
+    DEV_TRY(t.alloc(&d_tid, 256));
+    DEV_TRY(hipMemcpy(d_tb, tb.data(), (size_t)K * 4, hipMemcpyHostToDevice));
+    DEV_TRY(hipMemcpy(d_tid, tid.data(), (size_t)K, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(bd_ids_kernel, dim3(grid_of(n)), dim3(256), 0, s, n, d_val, d_tb, d_tid, K, d_ids);
-    BD_TRY(hipGetLastError());
-    BD_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -390,30 +343,30 @@ int devbuild_merge_stage(sm_matrix *m, hipStream_t s, hipError_t &err) {
     const int32_t *corner = reinterpret_cast<const int32_t *>(p.d_merge_corner);
     DevScratch t;
     uint8_t *ids = nullptr;
-    BD_TRY(t.alloc(&ids, nnz));
+    DEV_TRY(t.alloc(&ids, nnz));
     std::vector<float> table;
     const int rc = devbuild_codebook(m->d_val, nnz, table, ids, s, err);
     if (rc != 0) return rc;   // > 255 distinct values: declined (as codebook_ids)
     const int64_t nb = merge_blocks(m->n_rows, nnz);
     unsigned long long *key = nullptr, *skey = nullptr;
     int32_t *idx = nullptr, *sidx = nullptr;
-    BD_TRY(t.alloc(&key, nnz));
-    BD_TRY(t.alloc(&skey, nnz));
-    BD_TRY(t.alloc(&idx, nnz));
-    BD_TRY(t.alloc(&sidx, nnz));
+    DEV_TRY(t.alloc(&key, nnz));
+    DEV_TRY(t.alloc(&skey, nnz));
+    DEV_TRY(t.alloc(&idx, nnz));
+    DEV_TRY(t.alloc(&sidx, nnz));
     hipLaunchKernelGGL(bd_mkey_kernel, dim3((unsigned)std::min<int64_t>(nb, 1 << 16)), dim3(256), 0, s, nb, corner, col,
                        key, idx);
-    BD_TRY(hipGetLastError());
-    BD_TRY(sort_pairs(t, key, skey, idx, sidx, nnz, 24 + bits_for((uint32_t)std::max<int64_t>(nb - 1, 1)), s));
-    BD_TRY(m->mem.alloc(&p.d_mstage_w, nnz));
-    BD_TRY(m->mem.alloc(&p.d_mstage_z, nnz));
-    BD_TRY(m->mem.alloc(&p.d_mstage_tab, 256));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(dev_sort_pairs(t, key, skey, idx, sidx, nnz, 24 + bits_for((uint32_t)std::max<int64_t>(nb - 1, 1)), s));
+    DEV_TRY(m->mem.alloc(&p.d_mstage_w, nnz));
+    DEV_TRY(m->mem.alloc(&p.d_mstage_z, nnz));
+    DEV_TRY(m->mem.alloc(&p.d_mstage_tab, 256));
     table.resize(256, 0.0f);
-    BD_TRY(hipMemcpy(p.d_mstage_tab, table.data(), 256 * 4, hipMemcpyHostToDevice));
+    DEV_TRY(hipMemcpy(p.d_mstage_tab, table.data(), 256 * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(bd_mstage_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, skey, sidx, corner, col, ids,
                        p.d_mstage_w, p.d_mstage_z);
-    BD_TRY(hipGetLastError());
-    BD_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -428,91 +381,91 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
     uint8_t *ids = nullptr;
     bool cb = codebook && m->n_cols <= ((int64_t)1 << kSellCbColBits);
     if (cb) {
-        BD_TRY(t.alloc(&ids, nnz));
+        DEV_TRY(t.alloc(&ids, nnz));
         const int rc = devbuild_codebook(m->d_val, nnz, table, ids, s, err);
         if (rc < 0) return rc;
         cb = rc == 0;
     }
     // units
     int32_t *nu = nullptr, *np = nullptr, *lf = nullptr, *ubase = nullptr, *pbase = nullptr, *lbase = nullptr;
-    BD_TRY(t.alloc(&nu, nr + 1));
-    BD_TRY(t.alloc(&np, nr + 1));
-    BD_TRY(t.alloc(&lf, nr + 1));
-    BD_TRY(t.alloc(&ubase, nr + 1));
-    BD_TRY(t.alloc(&pbase, nr + 1));
-    BD_TRY(t.alloc(&lbase, nr + 1));
-    BD_TRY(hipMemsetAsync(nu + nr, 0, 4, s));
-    BD_TRY(hipMemsetAsync(np + nr, 0, 4, s));
-    BD_TRY(hipMemsetAsync(lf + nr, 0, 4, s));
+    DEV_TRY(t.alloc(&nu, nr + 1));
+    DEV_TRY(t.alloc(&np, nr + 1));
+    DEV_TRY(t.alloc(&lf, nr + 1));
+    DEV_TRY(t.alloc(&ubase, nr + 1));
+    DEV_TRY(t.alloc(&pbase, nr + 1));
+    DEV_TRY(t.alloc(&lbase, nr + 1));
+    DEV_TRY(hipMemsetAsync(nu + nr, 0, 4, s));
+    DEV_TRY(hipMemsetAsync(np + nr, 0, 4, s));
+    DEV_TRY(hipMemsetAsync(lf + nr, 0, 4, s));
     hipLaunchKernelGGL(bd_units_count_kernel, dim3(grid_of(nr)), dim3(256), 0, s, nr, m->d_row_ptr, max_len, nu, np, lf);
-    BD_TRY(hipGetLastError());
-    BD_TRY(excl_sum(t, nu, ubase, nr + 1, s));
-    BD_TRY(excl_sum(t, np, pbase, nr + 1, s));
-    BD_TRY(excl_sum(t, lf, lbase, nr + 1, s));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(dev_excl_sum(t, nu, ubase, nr + 1, s));
+    DEV_TRY(dev_excl_sum(t, np, pbase, nr + 1, s));
+    DEV_TRY(dev_excl_sum(t, lf, lbase, nr + 1, s));
     int32_t tot[3] = {0, 0, 0};
-    BD_TRY(hipMemcpyAsync(&tot[0], ubase + nr, 4, hipMemcpyDeviceToHost, s));
-    BD_TRY(hipMemcpyAsync(&tot[1], pbase + nr, 4, hipMemcpyDeviceToHost, s));
-    BD_TRY(hipMemcpyAsync(&tot[2], lbase + nr, 4, hipMemcpyDeviceToHost, s));
-    BD_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipMemcpyAsync(&tot[0], ubase + nr, 4, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipMemcpyAsync(&tot[1], pbase + nr, 4, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipMemcpyAsync(&tot[2], lbase + nr, 4, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipStreamSynchronize(s));
     const int64_t U = tot[0];
     const int32_t n_parts = tot[1], n_long = tot[2];
     SellDev &d = p.sell;
     d.max_len = max_len;
     d.n_long = n_long;
     const size_t mark = m->mem.mark();
-    BD_TRY(m->mem.alloc(&d.d_long_rows, n_long));
-    BD_TRY(m->mem.alloc(&d.d_long_ptr, n_long + 1));
-    BD_TRY(m->mem.alloc(&d.d_partials, n_parts));
-    BD_TRY(hipMemsetAsync(d.d_long_ptr, 0, 4, s));
+    DEV_TRY(m->mem.alloc(&d.d_long_rows, n_long));
+    DEV_TRY(m->mem.alloc(&d.d_long_ptr, n_long + 1));
+    DEV_TRY(m->mem.alloc(&d.d_partials, n_parts));
+    DEV_TRY(hipMemsetAsync(d.d_long_ptr, 0, 4, s));
     int32_t *urow = nullptr, *ustart = nullptr, *un = nullptr, *upart = nullptr, *uidx = nullptr, *order = nullptr;
     uint32_t *ukey = nullptr, *ukey_s = nullptr;
-    BD_TRY(t.alloc(&urow, U));
-    BD_TRY(t.alloc(&ustart, U));
-    BD_TRY(t.alloc(&un, U));
-    BD_TRY(t.alloc(&upart, U));
-    BD_TRY(t.alloc(&uidx, U));
-    BD_TRY(t.alloc(&order, U));
-    BD_TRY(t.alloc(&ukey, U));
-    BD_TRY(t.alloc(&ukey_s, U));
+    DEV_TRY(t.alloc(&urow, U));
+    DEV_TRY(t.alloc(&ustart, U));
+    DEV_TRY(t.alloc(&un, U));
+    DEV_TRY(t.alloc(&upart, U));
+    DEV_TRY(t.alloc(&uidx, U));
+    DEV_TRY(t.alloc(&order, U));
+    DEV_TRY(t.alloc(&ukey, U));
+    DEV_TRY(t.alloc(&ukey_s, U));
     hipLaunchKernelGGL(bd_units_emit_kernel, dim3(grid_of(nr)), dim3(256), 0, s, nr, m->d_row_ptr, max_len, ubase,
                        pbase, lbase, urow, ustart, un, upart, ukey, uidx, d.d_long_rows, d.d_long_ptr);
-    BD_TRY(hipGetLastError());
-    BD_TRY(sort_pairs(t, ukey, ukey_s, uidx, order, U, bits_for((uint32_t)max_len), s));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(dev_sort_pairs(t, ukey, ukey_s, uidx, order, U, bits_for((uint32_t)max_len), s));
     // slices
     const int64_t ns = (U + kSellLanes - 1) / kSellLanes;
     int64_t *slots = nullptr;
-    BD_TRY(t.alloc(&slots, ns + 1));
-    BD_TRY(m->mem.alloc(&d.d_off, ns));
-    BD_TRY(m->mem.alloc(&d.d_len, ns));
-    BD_TRY(hipMemsetAsync(slots + ns, 0, 8, s));
+    DEV_TRY(t.alloc(&slots, ns + 1));
+    DEV_TRY(m->mem.alloc(&d.d_off, ns));
+    DEV_TRY(m->mem.alloc(&d.d_len, ns));
+    DEV_TRY(hipMemsetAsync(slots + ns, 0, 8, s));
     hipLaunchKernelGGL(bd_slice_len_kernel, dim3(grid_of(ns)), dim3(256), 0, s, ns, U, order, un, d.d_len, slots);
-    BD_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     int64_t *offs = nullptr;
-    BD_TRY(t.alloc(&offs, ns + 1));
-    BD_TRY(excl_sum(t, slots, offs, ns + 1, s));
+    DEV_TRY(t.alloc(&offs, ns + 1));
+    DEV_TRY(dev_excl_sum(t, slots, offs, ns + 1, s));
     int64_t padded = 0;
-    BD_TRY(hipMemcpyAsync(&padded, offs + ns, 8, hipMemcpyDeviceToHost, s));
-    BD_TRY(hipMemcpyAsync(d.d_off, offs, (size_t)ns * 8, hipMemcpyDeviceToDevice, s));
-    BD_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipMemcpyAsync(&padded, offs + ns, 8, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipMemcpyAsync(d.d_off, offs, (size_t)ns * 8, hipMemcpyDeviceToDevice, s));
+    DEV_TRY(hipStreamSynchronize(s));
     if (ns == 0 || padded >= ((int64_t)1 << 31) - kSellLanes * kSellUnroll) {   // upload_sell declines
         m->mem.release_since(mark);
         d = SellDev();
         return 0;
     }
-    BD_TRY(m->mem.alloc(&d.d_row, ns * kSellLanes));
-    BD_TRY(m->mem.alloc(&d.d_row_len, ns * kSellLanes));
-    BD_TRY(hipMemsetAsync(d.d_row, 0xFF, (size_t)ns * kSellLanes * 4, s));   // -1: no row
-    BD_TRY(hipMemsetAsync(d.d_row_len, 0, (size_t)ns * kSellLanes * 4, s));
+    DEV_TRY(m->mem.alloc(&d.d_row, ns * kSellLanes));
+    DEV_TRY(m->mem.alloc(&d.d_row_len, ns * kSellLanes));
+    DEV_TRY(hipMemsetAsync(d.d_row, 0xFF, (size_t)ns * kSellLanes * 4, s));   // -1: no row
+    DEV_TRY(hipMemsetAsync(d.d_row_len, 0, (size_t)ns * kSellLanes * 4, s));
     const int64_t tail = 32 * kSellLanes;
-    BD_TRY(m->mem.alloc(&d.d_col, padded + tail));
-    BD_TRY(hipMemsetAsync(d.d_col, 0, (size_t)(padded + tail) * 4, s));
+    DEV_TRY(m->mem.alloc(&d.d_col, padded + tail));
+    DEV_TRY(hipMemsetAsync(d.d_col, 0, (size_t)(padded + tail) * 4, s));
     if (cb) {
-        BD_TRY(m->mem.alloc(&d.d_table, std::max<int64_t>((int64_t)table.size(), 1)));
-        if (!table.empty()) BD_TRY(hipMemcpy(d.d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice));
+        DEV_TRY(m->mem.alloc(&d.d_table, std::max<int64_t>((int64_t)table.size(), 1)));
+        if (!table.empty()) DEV_TRY(hipMemcpy(d.d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice));
         d.table_size = (int32_t)table.size();
     } else {
-        BD_TRY(m->mem.alloc(&d.d_val, padded + tail));
-        BD_TRY(hipMemsetAsync(d.d_val, 0, (size_t)(padded + tail) * 4, s));
+        DEV_TRY(m->mem.alloc(&d.d_val, padded + tail));
+        DEV_TRY(hipMemsetAsync(d.d_val, 0, (size_t)(padded + tail) * 4, s));
     }
     const unsigned gf = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ns + 3) / 4, 1 << 16));
     if (cb)
@@ -521,8 +474,8 @@ int devbuild_sell(sm_matrix *m, int32_t max_len, bool codebook, hipStream_t s, h
     else
         hipLaunchKernelGGL(bd_fill_kernel<false>, dim3(gf), dim3(256), 0, s, ns, U, order, urow, ustart, un, upart,
                            d.d_off, col, m->d_val, ids, d.d_row, d.d_row_len, d.d_col, d.d_val);
-    BD_TRY(hipGetLastError());
-    BD_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipStreamSynchronize(s));
     d.n_slices = ns;
     return 0;
 }

@@ -2,18 +2,14 @@
 // codebook words) built on the device from a device CSR: the bytes band2.cpp's band2_build
 // produces, as layouts.cpp's build_band2 chooses them, without copying the terms to the host
 // and the layout back.  The placement heuristics are band2_place.h, the code the host runs.
+// The sorted run of terms, the tile starts, the scan of the band counts and the LDS sort / scan /
+// segment routines are builddev_tiles.h, shared with builddev_gcb.hip; band2's own:
 //
-//   keys    per term: its row (a search in row_ptr), key = block << cbits | column, and the
-//           check that the row's columns strictly ascend (band2_build declines otherwise);
-//   sort    one stable radix sort of (key, term) over the used bits: a tile (block, slab) is a
-//           contiguous run ordered by (column, row), and every band a contiguous sub-run of it --
-//           also the by-row pieces of a hub column;
 //   cut     one workgroup per tile replays build_tile's loop: the band's last column from the
 //           window and the term capacity (a look-up in the sorted run), the cut inside a row
 //           segment too long for one chunk, the 31/32 shrink until the by-row segments pack
-//           into the band's chunks, the by-row split of a one-column band.  A band's terms are
-//           ordered by (row, position) with a bitonic sort in LDS, the segments come from two
-//           block scans, one thread replays the packing;
+//           into the band's chunks, the by-row split of a one-column band (the by-row pieces of
+//           a hub column are contiguous sub-runs too).  One thread replays the packing;
 //   choose  on the host, from the band count alone (every term lands in a band): dma3 bands
 //           first, wide ones where those would be under 70 % full, else declined;
 //   emit    one wave per band repeats the sort and the segments of its run, balances its chunks
@@ -21,12 +17,11 @@
 //           ballot), places each chunk's lanes with one lane per chunk, and writes the image
 //           from LDS in one coalesced pass.  (One thread per band for the balance took 1.3 s on
 //           config 2, against 0.38 s on the host and 0.12 s this way: profiles/band_devbuild.txt.)
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <vector>
 
 #include "band2_place.h"
+#include "builddev_tiles.h"
 #include "sm_internal.h"
 #include "xband.h"
 
@@ -34,77 +29,13 @@ namespace smamd {
 namespace {
 
 constexpr int kNT = 256;                 // threads of a cut workgroup
-constexpr int kSortN = 2048;             // a band's terms at most (32 chunks of 64), the bitonic width
 constexpr int kET = 64;                  // threads of an emit workgroup: one wave
-constexpr int kPosBits = 11;
-constexpr uint32_t kPosMask = (1u << kPosBits) - 1u;
-constexpr uint32_t kPad = 0xFFFFFFFFu;
-constexpr int kMaxChunks = 32;
+constexpr int kMaxChunks = 32;           // of 64 terms: kSortN
 constexpr int kRowsLog2 = 14;            // both kernel geometries: 16K-row blocks
 static_assert(kB2Wide.block_rows == 1 << kRowsLog2 && kB2Dma3Cb.block_rows == 1 << kRowsLog2 &&
                   kB2Dma3B2.block_rows == 1 << kRowsLog2,
               "row keys: rows in block below kRowsLog2 bits");
 static_assert(kRowsLog2 + kPosBits <= 31, "sort key: row in block | position, below the pad");
-
-unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
-
-#define GS_LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-// One thread per term: key, row in block, term index; flag 1 = a row's columns not strictly
-// ascending.
-__global__ __launch_bounds__(256) void b2_keys_kernel(int64_t nnz, int64_t n_rows, const int32_t *__restrict__ rp,
-                                                      const int32_t *__restrict__ col, int cbits,
-                                                      unsigned long long *__restrict__ key, int32_t *__restrict__ idx,
-                                                      int32_t *__restrict__ rowl, int32_t *__restrict__ flag) {
-    GS_LOOP(e, nnz) {
-        int64_t lo = 0, hi = n_rows;   // the first r with rp[r] > e (rp[n_rows] = nnz > e)
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)rp[mid] <= e) lo = mid + 1;
-            else hi = mid;
-        }
-        const int64_t r = lo - 1;
-        const int32_t c = col[e];
-        if (e > (int64_t)rp[r] && c <= col[e - 1]) atomicOr(flag, 1);
-        key[e] = ((unsigned long long)(r >> kRowsLog2) << cbits) | (unsigned)c;
-        idx[e] = (int32_t)e;
-        rowl[e] = (int32_t)(r & ((1 << kRowsLog2) - 1));
-    }
-}
-
-// Sorted order: column, row in block, and the value bits or the codebook id.
-__global__ __launch_bounds__(256) void b2_gather_kernel(int64_t n, const unsigned long long *__restrict__ skey,
-                                                        const int32_t *__restrict__ sidx, const int32_t *__restrict__ rowl,
-                                                        const float *__restrict__ val, const uint8_t *__restrict__ ids,
-                                                        unsigned long long cmask, int32_t *__restrict__ scol,
-                                                        int32_t *__restrict__ srl, uint32_t *__restrict__ sv) {
-    GS_LOOP(i, n) {
-        const int32_t e = sidx[i];
-        scol[i] = (int32_t)(skey[i] & cmask);
-        srl[i] = rowl[e];
-        sv[i] = ids ? (uint32_t)ids[e] : __float_as_uint(val[e]);
-    }
-}
-
-// Tile t = b * S + s starts at the first key >= (b << cbits) + the slab's first column.
-__global__ __launch_bounds__(256) void b2_tile_start_kernel(int64_t n_tiles, B2Slabs sl, int cbits, int64_t n,
-                                                            const unsigned long long *__restrict__ skey,
-                                                            int32_t *__restrict__ tts) {
-    GS_LOOP(t, n_tiles + 1) {
-        if (t == n_tiles) {
-            tts[t] = (int32_t)n;
-            continue;
-        }
-        const unsigned long long want = ((unsigned long long)(t / sl.ns) << cbits) + (unsigned long long)sl.lo(t % sl.ns);
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (skey[mid] < want) lo = mid + 1;
-            else hi = mid;
-        }
-        tts[t] = (int32_t)lo;
-    }
-}
 
 // LDS of one band's packing.
 struct BandLds {
@@ -126,96 +57,22 @@ __device__ __forceinline__ int64_t lower_bound_dev(const int32_t *__restrict__ v
     return lo;
 }
 
-// Exclusive block scan of one count per thread; the total in *tot.  Ends with a barrier.
-template <int NT>
-__device__ __forceinline__ int block_scan(BandLds &L, int v, int *tot) {
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += u;
+// Where band_segments writes band2's segment records.
+struct B2Segs {
+    BandLds &L;
+    __device__ void head(int q, int j, int rl) const {
+        L.segs[q].rl = rl;
+        L.segs[q].s = j;
     }
-    if (lane == 63) L.wsum[w] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < NT / 64; ++k) {
-        const int s = L.wsum[k];
-        before += k < w ? s : 0;
-        all += s;
-    }
-    __syncthreads();   // wsum reused by the next scan
-    *tot = all;
-    return before + inc - v;
-}
+    __device__ void entry(int, int) const {}
+    __device__ void end(int nseg, int len) const { L.segs[nseg].s = len; }
+};
 
-// Loads the run [a, a + n) (n <= kSortN) and sorts it by (row, position).
+// band_segments into L.segs, with every segment's length.  Ends with a barrier.
 template <int NT>
-__device__ void band_sort(BandLds &L, const int32_t *__restrict__ srl, int64_t a, int n) {
-    const int t = threadIdx.x;
-    for (int j = t; j < kSortN; j += NT) L.key[j] = j < n ? ((uint32_t)srl[a + j] << kPosBits) | (uint32_t)j : kPad;
-    __syncthreads();
-    for (int k = 2; k <= kSortN; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int p = t; p < kSortN / 2; p += NT) {
-                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                const int l = i | j;
-                const uint32_t x = L.key[i], y = L.key[l];
-                const bool up = (i & k) == 0;
-                if ((x > y) == up) {
-                    L.key[i] = y;
-                    L.key[l] = x;
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// The sorted run's entries of position < len, in (row, position) order, and their segments by
-// row (build_tile's per-row runs inside the band).  Returns the segment count; ends with a
-// barrier.  L.key is only read.
-template <int NT>
-__device__ int band_segments(BandLds &L, int len) {
-    const int t = threadIdx.x;
-    uint32_t k[(kSortN / NT)];
-    int v = 0;
-#pragma unroll
-    for (int u = 0; u < (kSortN / NT); ++u) {
-        k[u] = L.key[t * (kSortN / NT) + u];
-        v += k[u] != kPad && (int)(k[u] & kPosMask) < len;
-    }
-    int tot;
-    int p = block_scan<NT>(L, v, &tot);
-#pragma unroll
-    for (int u = 0; u < (kSortN / NT); ++u)
-        if (k[u] != kPad && (int)(k[u] & kPosMask) < len) {
-            L.crl[p] = (uint16_t)(k[u] >> kPosBits);
-            L.cpos[p] = (uint16_t)(k[u] & kPosMask);
-            ++p;
-        }
-    __syncthreads();
-    // tot == len: every position < len is in the run exactly once.
-    int h = 0;
-#pragma unroll
-    for (int u = 0; u < (kSortN / NT); ++u) {
-        const int j = t * (kSortN / NT) + u;
-        h += j < len && (j == 0 || L.crl[j] != L.crl[j - 1]);
-    }
-    int nseg;
-    int q = block_scan<NT>(L, h, &nseg);
-#pragma unroll
-    for (int u = 0; u < (kSortN / NT); ++u) {
-        const int j = t * (kSortN / NT) + u;
-        if (j < len && (j == 0 || L.crl[j] != L.crl[j - 1])) {
-            L.segs[q].rl = L.crl[j];
-            L.segs[q].s = j;
-            ++q;
-        }
-    }
-    if (t == 0) L.segs[nseg].s = len;
-    __syncthreads();
-    for (int g = t; g < nseg; g += NT) L.segs[g].n = L.segs[g + 1].s - L.segs[g].s;
+__device__ int b2_segments(BandLds &L, int len) {
+    const int nseg = band_segments<NT>(L, len, B2Segs{L});
+    for (int g = threadIdx.x; g < nseg; g += NT) L.segs[g].n = L.segs[g + 1].s - L.segs[g].s;
     __syncthreads();
     return nseg;
 }
@@ -253,7 +110,7 @@ __global__ __launch_bounds__(kNT) void b2_cut_kernel(int64_t n_tiles, B2Slabs sl
             for (;;) {   // pack; shrink chi until the band fits
                 const bool single = chi == clo + 1;
                 if (t == 0) L.cut = INT32_MAX;
-                const int nseg = band_segments<kNT>(L, len);
+                const int nseg = b2_segments<kNT>(L, len);
                 // A row's segment longer than a chunk (band2: the rank field) cuts the band at
                 // that row's first column past it.
                 for (int g = t; g < nseg; g += kNT)
@@ -299,20 +156,6 @@ __global__ __launch_bounds__(kNT) void b2_cut_kernel(int64_t n_tiles, B2Slabs sl
             a += max(len, 1);   // a band holds its first term at least
         }
         if (t == 0) nbands[tile] = nb;
-    }
-}
-
-// Band starts by global band index, and each band's tile.
-__global__ __launch_bounds__(256) void b2_compact_kernel(int64_t n_tiles, const int32_t *__restrict__ tts,
-                                                         const int32_t *__restrict__ tbs,
-                                                         const int32_t *__restrict__ bstart,
-                                                         int32_t *__restrict__ gstart, int32_t *__restrict__ gtile) {
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int32_t b0 = tbs[tile], nb = tbs[tile + 1] - b0;
-        for (int32_t k = threadIdx.x; k < nb; k += blockDim.x) {
-            gstart[b0 + k] = bstart[tts[tile] + k];
-            gtile[b0 + k] = (int32_t)tile;
-        }
     }
 }
 
@@ -464,7 +307,7 @@ __global__ __launch_bounds__(kET) void b2_emit_kernel(int64_t n_bands, const int
         }
         for (int i = t; i < band_words; i += kET) img[i] = 0u;   // dummies: word 0, value 0
         band_sort<kET>(L, srl, a, n);
-        const int nseg = band_segments<kET>(L, n);
+        const int nseg = b2_segments<kET>(L, n);
         const int32_t clo_al = scol[a] & ~3;
         for (int j = t; j < n; j += kET) {
             const int p = L.cpos[j];
@@ -515,16 +358,8 @@ __global__ __launch_bounds__(kET) void b2_emit_kernel(int64_t n_bands, const int
     }
 }
 
-#define B2_TRY(x)                  \
-    do {                           \
-        const hipError_t e_ = (x); \
-        if (e_ != hipSuccess) {    \
-            err = e_;              \
-            return -5;             \
-        }                          \
-    } while (0)
-
-// A scratch allocation: out of memory declines to the host builder (the error is cleared).
+// A step that allocates scratch: out of memory declines to the host builder (the error is
+// cleared).  devbuild_gcb reports the same condition as an error; the two are not unified here.
 #define B2_SCRATCH(x)                                    \
     do {                                                 \
         const hipError_t e_ = (x);                       \
@@ -537,12 +372,6 @@ __global__ __launch_bounds__(kET) void b2_emit_kernel(int64_t n_bands, const int
             return -5;                                   \
         }                                                \
     } while (0)
-
-int bits_for(uint64_t v) {
-    int b = 1;
-    while (b < 64 && (v >> b) != 0) ++b;
-    return b;
-}
 
 // band2_build's checks of a geometry.
 bool geom_ok(const B2Geom &g, bool cb) {
@@ -570,8 +399,6 @@ int devbuild_band2(sm_matrix *m, int32_t kind, int32_t geo_opt, int32_t n_slabs,
     const B2Slabs sl = b2_slabs(n_cols, n_slabs, slab0_permille);
     const int64_t ntile = nblk * sl.ns;
     if (ntile >= ((int64_t)1 << 30)) return 1;
-    const int cbits = bits_for((uint64_t)(n_cols - 1));
-    const int end_bit = cbits + bits_for((uint64_t)std::max<int64_t>(nblk - 1, 1));
     DevScratch tp;
     // Codebook words where the values allow (first-occurrence ids, the host's order), else --
     // or for kind band2 -- 8-byte entries.
@@ -593,48 +420,9 @@ int devbuild_band2(sm_matrix *m, int32_t kind, int32_t geo_opt, int32_t n_slabs,
             table.clear();
         }
     }
-    unsigned long long *key = nullptr, *skey = nullptr;
-    int32_t *idx = nullptr, *sidx = nullptr, *rowl = nullptr, *flag = nullptr;
-    B2_SCRATCH(tp.alloc(&key, nnz));
-    B2_SCRATCH(tp.alloc(&skey, nnz));
-    B2_SCRATCH(tp.alloc(&idx, nnz));
-    B2_SCRATCH(tp.alloc(&sidx, nnz));
-    B2_SCRATCH(tp.alloc(&rowl, nnz));
-    B2_SCRATCH(tp.alloc(&flag, 1));
-    B2_TRY(hipMemsetAsync(flag, 0, 4, s));
-    hipLaunchKernelGGL(b2_keys_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, n_rows, m->d_row_ptr, m->d_col, cbits,
-                       key, idx, rowl, flag);
-    B2_TRY(hipGetLastError());
-    {
-        size_t bytes = 0;
-        B2_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, idx, sidx, (int)nnz, 0, end_bit, s));
-        uint8_t *tmp = nullptr;
-        B2_SCRATCH(tp.alloc(&tmp, (int64_t)bytes));
-        B2_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, skey, idx, sidx, (int)nnz, 0, end_bit, s));
-        B2_TRY(hipStreamSynchronize(s));
-        tp.release(tmp);
-    }
-    int32_t fl = 0;
-    B2_TRY(hipMemcpyAsync(&fl, flag, 4, hipMemcpyDeviceToHost, s));
-    B2_TRY(hipStreamSynchronize(s));
-    if (fl) return 1;   // a row's columns not strictly ascending (band2_build declines)
-    tp.release(key);
-    tp.release(idx);
-    int32_t *scol = nullptr, *srl = nullptr, *tts = nullptr;
-    uint32_t *sv = nullptr;
-    B2_SCRATCH(tp.alloc(&scol, nnz));
-    B2_SCRATCH(tp.alloc(&srl, nnz));
-    B2_SCRATCH(tp.alloc(&sv, nnz));
-    B2_SCRATCH(tp.alloc(&tts, ntile + 1));
-    const unsigned long long cmask = ((unsigned long long)1 << cbits) - 1;
-    hipLaunchKernelGGL(b2_gather_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, skey, sidx, rowl, m->d_val, ids, cmask,
-                       scol, srl, sv);
-    hipLaunchKernelGGL(b2_tile_start_kernel, dim3(grid_of(ntile + 1)), dim3(256), 0, s, ntile, sl, cbits, nnz, skey, tts);
-    B2_TRY(hipGetLastError());
-    B2_TRY(hipStreamSynchronize(s));
-    tp.release(skey);
-    tp.release(sidx);
-    tp.release(rowl);
+    TileRun run;
+    B2_SCRATCH(run_tile_front(tp, m, ids, kRowsLog2, nblk, sl, run, s));
+    if (run.unsorted) return 1;   // a row's columns not strictly ascending (band2_build declines)
     if (ids) tp.release(ids);
     // cut: build_band2's sequence of geometries -- dma3 unless the wide one is asked for, wide
     // where the dma3 bands would be mostly padding
@@ -642,21 +430,17 @@ int devbuild_band2(sm_matrix *m, int32_t kind, int32_t geo_opt, int32_t n_slabs,
     B2_SCRATCH(tp.alloc(&bstart, nnz));
     B2_SCRATCH(tp.alloc(&nb, ntile + 1));
     B2_SCRATCH(tp.alloc(&tbs, ntile + 1));
-    uint8_t *scan_tmp = nullptr;
-    size_t scan_bytes = 0;
-    B2_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nb, tbs, (int)(ntile + 1), s));
-    B2_SCRATCH(tp.alloc(&scan_tmp, (int64_t)scan_bytes));
+    BandScan scan;
+    B2_SCRATCH(scan.prepare(tp, ntile));
     B2Geom g = geo_opt != 6 ? (cb ? kB2Dma3Cb : kB2Dma3B2) : kB2Wide;
     int32_t n_bands = 0;
     for (;;) {
         if (!geom_ok(g, cb)) return 1;
-        B2_TRY(hipMemsetAsync(nb + ntile, 0, 4, s));
+        DEV_TRY(hipMemsetAsync(nb + ntile, 0, 4, s));
         hipLaunchKernelGGL(b2_cut_kernel, dim3((unsigned)std::min<int64_t>(ntile, 1 << 16)), dim3(kNT), 0, s, ntile, sl,
-                           tts, scol, srl, g, cb ? 1 : 0, bstart, nb);
-        B2_TRY(hipGetLastError());
-        B2_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, nb, tbs, (int)(ntile + 1), s));
-        B2_TRY(hipMemcpyAsync(&n_bands, tbs + ntile, 4, hipMemcpyDeviceToHost, s));
-        B2_TRY(hipStreamSynchronize(s));
+                           run.tts, run.scol, run.srl, g, cb ? 1 : 0, bstart, nb);
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(scan.run(nb, tbs, &n_bands, s));
         // band2_build: 32-bit entry offsets; build_band2: bands at least 70 % full unless forced
         // (every term lands in a band: real_terms = nnz)
         const bool ok = (int64_t)n_bands * 4096 < ((int64_t)1 << 31) &&
@@ -668,22 +452,20 @@ int devbuild_band2(sm_matrix *m, int32_t kind, int32_t geo_opt, int32_t n_slabs,
     if (n_bands <= 0) return 1;
     const int64_t band_words = (int64_t)(cb ? 64 : 128) * g.chunks();
     int32_t *gstart = nullptr, *gtile = nullptr;
-    B2_SCRATCH(tp.alloc(&gstart, n_bands));
-    B2_SCRATCH(tp.alloc(&gtile, n_bands));
-    hipLaunchKernelGGL(b2_compact_kernel, dim3((unsigned)std::min<int64_t>(ntile, 1 << 16)), dim3(256), 0, s, ntile, tts,
-                       tbs, bstart, gstart, gtile);
-    B2_TRY(hipGetLastError());
+    B2_SCRATCH(compact_bands(tp, run, tbs, bstart, n_bands, &gstart, &gtile, s));
     // the layout's arrays: build_band2's allocations
     Band2Dev &d = m->plan.b2;
-    B2_TRY(m->mem.alloc(&d.d_tile_band, ntile + 1));
-    B2_TRY(m->mem.alloc(&d.d_band_clo, std::max<int64_t>(1, n_bands)));
-    B2_TRY(m->mem.alloc(&d.d_ent, std::max<int64_t>(1, n_bands * band_words)));
-    B2_TRY(hipMemcpyAsync(d.d_tile_band, tbs, (size_t)(ntile + 1) * 4, hipMemcpyDeviceToDevice, s));
+    DEV_TRY(m->mem.alloc(&d.d_tile_band, ntile + 1));
+    DEV_TRY(m->mem.alloc(&d.d_band_clo, std::max<int64_t>(1, n_bands)));
+    DEV_TRY(m->mem.alloc(&d.d_ent, std::max<int64_t>(1, n_bands * band_words)));
+    DEV_TRY(hipMemcpyAsync(d.d_tile_band, tbs, (size_t)(ntile + 1) * 4, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(b2_emit_kernel, dim3((unsigned)std::min<int64_t>(n_bands, 1 << 20)), dim3(kET), 0, s,
-                       (int64_t)n_bands, tts, gstart, gtile, scol, srl, sv, g, cb ? 1 : 0, d.d_band_clo, d.d_ent, flag);
-    B2_TRY(hipGetLastError());
-    B2_TRY(hipMemcpyAsync(&fl, flag, 4, hipMemcpyDeviceToHost, s));
-    B2_TRY(hipStreamSynchronize(s));
+                       (int64_t)n_bands, run.tts, gstart, gtile, run.scol, run.srl, run.sval, g, cb ? 1 : 0, d.d_band_clo,
+                       d.d_ent, run.flag);
+    DEV_TRY(hipGetLastError());
+    int32_t fl = 0;
+    DEV_TRY(hipMemcpyAsync(&fl, run.flag, 4, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipStreamSynchronize(s));
     if (fl) {   // the emission's packing disagreed with the cut's: a builder bug, not a decline
         err = hipErrorUnknown;
         return -6;

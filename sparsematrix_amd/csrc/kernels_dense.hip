@@ -33,11 +33,10 @@
 //
 // Integer atomics on LDS and global counters only; every launch geometry is a function of
 // (n_rows, n_cols, the alignment class of w and ld) alone.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstring>
 
+#include "devprim.h"
 #include "prune_select.h"
 #include "sm_internal.h"
 
@@ -371,17 +370,17 @@ hipError_t dense_mask_body(const float *fw, int64_t n_rows, int64_t n_cols, int6
     const bool vec = aligned16(fw) && (linear || (n_cols % 4 == 0 && ld % 4 == 0));
     uint8_t *keep = nullptr;
     uint32_t *cnt = nullptr, *base = nullptr;
-    PR_TRY(t.alloc(&keep, n_chunks * kSddmmChunk));
-    PR_TRY(t.alloc(&cnt, n_chunks + 1));
-    PR_TRY(t.alloc(&base, n_chunks + 1));
+    DEV_TRY_RET(t.alloc(&keep, n_chunks * kSddmmChunk));
+    DEV_TRY_RET(t.alloc(&cnt, n_chunks + 1));
+    DEV_TRY_RET(t.alloc(&base, n_chunks + 1));
     // The producers write the live elements only (the flag kernel: up to the next multiple of 4).
-    PR_TRY(hipMemsetAsync(keep + (n_chunks - 1) * kSddmmChunk, 0, kSddmmChunk, s));
-    PR_TRY(hipMemsetAsync(cnt + n_chunks, 0, sizeof(uint32_t), s));
+    DEV_TRY_RET(hipMemsetAsync(keep + (n_chunks - 1) * kSddmmChunk, 0, kSddmmChunk, s));
+    DEV_TRY_RET(hipMemsetAsync(cnt + n_chunks, 0, sizeof(uint32_t), s));
     const unsigned chunk_grid = p_grid(n_chunks, 1);
     size_t scan_bytes = 0;
     uint8_t *scan_tmp = nullptr;
-    PR_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, cnt, base, (int)(n_chunks + 1), s));
-    PR_TRY(t.alloc(&scan_tmp, (int64_t)scan_bytes));
+    DEV_TRY_RET(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, cnt, base, (int)(n_chunks + 1), s));
+    DEV_TRY_RET(t.alloc(&scan_tmp, (int64_t)scan_bytes));
 
     bool row_select = mode == SM_PRUNE_ROW_TOPK && count < n_cols;
     if (row_select) {
@@ -404,8 +403,8 @@ hipError_t dense_mask_body(const float *fw, int64_t n_rows, int64_t n_cols, int6
         if (mode == SM_PRUNE_THRESHOLD && float_key(threshold) > 0) K_arg = float_key(threshold) - 1, r_arg = 0;
         if (mode == SM_PRUNE_GLOBAL_TOPK && k < E) {   // 1 <= k < E: the caller took k == 0
             PruneState *st = nullptr;
-            PR_TRY(t.alloc(&st, 1));
-            PR_TRY(hipMemsetAsync(st, 0, sizeof(PruneState), s));
+            DEV_TRY_RET(t.alloc(&st, 1));
+            DEV_TRY_RET(hipMemsetAsync(st, 0, sizeof(PruneState), s));
             const unsigned grid = std::min(p_grid((int64_t)((E + 3) >> 2)), kPHistBlocks);
             for (int pass = 0; pass < 4; ++pass) {
                 if (vec) hipLaunchKernelGGL(dense_hist_kernel<true>, dim3(grid), dim3(kPThreads), 0, s, d, pass, st);
@@ -414,8 +413,8 @@ hipError_t dense_mask_body(const float *fw, int64_t n_rows, int64_t n_cols, int6
             }
             if (vec) hipLaunchKernelGGL(dense_equals_kernel<true>, dim3(chunk_grid), dim3(kPThreads), 0, s, d, n_chunks, st, cnt);
             else hipLaunchKernelGGL(dense_equals_kernel<false>, dim3(chunk_grid), dim3(kPThreads), 0, s, d, n_chunks, st, cnt);
-            PR_TRY(hipGetLastError());
-            PR_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, cnt, base, (int)(n_chunks + 1), s));
+            DEV_TRY_RET(hipGetLastError());
+            DEV_TRY_RET(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, cnt, base, (int)(n_chunks + 1), s));
             d_st = st;
         }
         if (vec)
@@ -426,11 +425,11 @@ hipError_t dense_mask_body(const float *fw, int64_t n_rows, int64_t n_cols, int6
                                r_arg, base, keep);
     }
     hipLaunchKernelGGL(dense_count_kernel, dim3(chunk_grid), dim3(kPThreads), 0, s, keep, n_chunks, cnt);
-    PR_TRY(hipGetLastError());
-    PR_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, cnt, base, (int)(n_chunks + 1), s));
+    DEV_TRY_RET(hipGetLastError());
+    DEV_TRY_RET(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, cnt, base, (int)(n_chunks + 1), s));
     uint32_t total = 0;
-    PR_TRY(hipMemcpyAsync(&total, base + n_chunks, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    PR_TRY(hipStreamSynchronize(s));
+    DEV_TRY_RET(hipMemcpyAsync(&total, base + n_chunks, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DEV_TRY_RET(hipStreamSynchronize(s));
     *keep_out = keep;
     *base_out = base;
     *kept = (int64_t)total;

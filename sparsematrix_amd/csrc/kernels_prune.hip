@@ -40,11 +40,10 @@
 // Integer atomics only (LDS and global counters: counts are exact, their order reaches nothing);
 // every launch geometry is a function of nnz and n_rows alone; every kernel strides over its
 // terms, chunks or rows with a capped grid.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstring>
 
+#include "devprim.h"
 #include "prune_select.h"
 #include "sm_internal.h"
 
@@ -390,10 +389,10 @@ hipError_t prune_mask_body(const int32_t *rp, const float *fval, int64_t n_rows,
         if (k > 0 && k < nnz) {
             PruneState *st = nullptr;
             int32_t *d_cnt = nullptr;
-            PR_TRY(t.alloc(&st, 1));
-            PR_TRY(t.alloc(&d_cnt, n_chunks));
-            PR_TRY(t.alloc(&d_base, n_chunks));
-            PR_TRY(hipMemsetAsync(st, 0, sizeof(PruneState), s));
+            DEV_TRY_RET(t.alloc(&st, 1));
+            DEV_TRY_RET(t.alloc(&d_cnt, n_chunks));
+            DEV_TRY_RET(t.alloc(&d_base, n_chunks));
+            DEV_TRY_RET(hipMemsetAsync(st, 0, sizeof(PruneState), s));
             const unsigned grid = std::min(p_grid((nnz + 3) >> 2), kPHistBlocks);
             for (int pass = 0; pass < 4; ++pass) {
                 hipLaunchKernelGGL(prune_hist_kernel, dim3(grid), dim3(kPThreads), 0, s, nnz, val, pass, st);
@@ -401,12 +400,8 @@ hipError_t prune_mask_body(const int32_t *rp, const float *fval, int64_t n_rows,
             }
             hipLaunchKernelGGL(prune_equals_kernel, dim3(p_grid(n_chunks, 1)), dim3(kPThreads), 0, s, nnz, n_chunks, val,
                                st, d_cnt);
-            PR_TRY(hipGetLastError());
-            size_t bytes = 0;
-            PR_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_cnt, d_base, (int)n_chunks, s));
-            uint8_t *tmp = nullptr;
-            PR_TRY(t.alloc(&tmp, (int64_t)bytes));
-            PR_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_cnt, d_base, (int)n_chunks, s));
+            DEV_TRY_RET(hipGetLastError());
+            DEV_TRY_RET(dev_excl_sum(t, d_cnt, d_base, n_chunks, s));
             d_st = st;
         }
         const unsigned grid = p_grid(n_chunks, 1);
@@ -416,8 +411,8 @@ hipError_t prune_mask_body(const int32_t *rp, const float *fval, int64_t n_rows,
         else
             hipLaunchKernelGGL(prune_flag_kernel<false>, dim3(grid), dim3(kPThreads), 0, s, nnz, n_chunks, val, d_st,
                                K_arg, r_arg, d_base, keep);
-        PR_TRY(hipGetLastError());
-        PR_TRY(hipStreamSynchronize(s));
+        DEV_TRY_RET(hipGetLastError());
+        DEV_TRY_RET(hipStreamSynchronize(s));
         if (kept) *kept = k;
         return hipSuccess;
     }
@@ -427,7 +422,7 @@ hipError_t prune_mask_body(const int32_t *rp, const float *fval, int64_t n_rows,
     if (mode == SM_PRUNE_THRESHOLD) {
         const unsigned grid = n_parts = p_grid((nnz + 3) >> 2);
         const uint32_t tkey = float_key(threshold);
-        PR_TRY(t.alloc(&d_parts, n_parts));
+        DEV_TRY_RET(t.alloc(&d_parts, n_parts));
         if (packed)
             hipLaunchKernelGGL(prune_threshold_kernel<true>, dim3(grid), dim3(kPThreads), 0, s, nnz, val, tkey, keep,
                                d_parts);
@@ -438,19 +433,19 @@ hipError_t prune_mask_body(const int32_t *rp, const float *fval, int64_t n_rows,
         int32_t *d_list = nullptr, *d_n = nullptr;
         const unsigned wave_grid = p_grid(n_rows, kRowBundle * kPWaves), group_grid = p_grid(n_rows, 1);
         n_parts = wave_grid + group_grid;
-        PR_TRY(t.alloc(&d_parts, n_parts));
-        PR_TRY(t.alloc(&d_list, n_rows));
-        PR_TRY(t.alloc(&d_n, 1));
-        PR_TRY(hipMemsetAsync(d_n, 0, sizeof(int32_t), s));
+        DEV_TRY_RET(t.alloc(&d_parts, n_parts));
+        DEV_TRY_RET(t.alloc(&d_list, n_rows));
+        DEV_TRY_RET(t.alloc(&d_n, 1));
+        DEV_TRY_RET(hipMemsetAsync(d_n, 0, sizeof(int32_t), s));
         hipLaunchKernelGGL(prune_row_wave_kernel, dim3(wave_grid), dim3(kPThreads), 0, s, n_rows, rp, val, count, keep,
                            d_list, d_n, d_parts);
         hipLaunchKernelGGL(prune_row_group_kernel, dim3(group_grid), dim3(kPThreads), 0, s, d_list, d_n, rp, val, count,
                            keep, d_parts + wave_grid);
     }
-    PR_TRY(hipGetLastError());
+    DEV_TRY_RET(hipGetLastError());
     std::vector<uint32_t> h_parts(n_parts);
-    PR_TRY(hipMemcpyAsync(h_parts.data(), d_parts, (size_t)n_parts * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    PR_TRY(hipStreamSynchronize(s));
+    DEV_TRY_RET(hipMemcpyAsync(h_parts.data(), d_parts, (size_t)n_parts * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DEV_TRY_RET(hipStreamSynchronize(s));
     if (kept) {
         int64_t sum = 0;
         for (const uint32_t v : h_parts) sum += v;
@@ -477,11 +472,7 @@ hipError_t prune_positions_device(int64_t nnz, const uint8_t *keep, int32_t *pos
         DevScratch t;
         hipcub::CountingInputIterator<int64_t> idx(0);
         hipcub::TransformInputIterator<int32_t, KeepFlag, hipcub::CountingInputIterator<int64_t>> in(idx, KeepFlag{keep, nnz});
-        size_t bytes = 0;
-        uint8_t *tmp = nullptr;
-        e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, pos, (int)(nnz + 1), s);
-        if (e == hipSuccess) e = t.alloc(&tmp, (int64_t)bytes);
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, pos, (int)(nnz + 1), s);
+        e = dev_excl_sum(t, in, pos, nnz + 1, s);
         if (e == hipSuccess) e = hipMemcpyAsync(&last, pos + nnz, sizeof(int32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }

@@ -31,10 +31,9 @@
 // No atomics; every launch geometry is a function of (n_rows, nnzA, nnzB); the result is a function
 // of the operands alone.  Products and the add are __fmul_rn / __fadd_rn: two separately rounded
 // products and one add, never a fused multiply-add.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 
+#include "devprim.h"
 #include "sm_internal.h"
 
 namespace smamd {
@@ -47,12 +46,6 @@ constexpr int64_t kSumMaxBlocks = 2048;                // 256 CUs x 8; the rest 
 unsigned sum_grid(int64_t items, int64_t per_block) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, kSumMaxBlocks));
 }
-
-#define SUM_TRY(x)                       \
-    do {                                 \
-        const hipError_t e_ = (x);       \
-        if (e_ != hipSuccess) return e_; \
-    } while (0)
 
 // kernels_sddmm.hip's row_of_term: the largest r in [lo, lo + len) with rp[r] <= e.
 __device__ __forceinline__ int32_t sum_row_of_term(const int32_t *__restrict__ rp, int32_t lo, int32_t len, int32_t e) {
@@ -203,37 +196,29 @@ hipError_t sum_count_body(int64_t n_rows, int64_t nnz_a, int64_t nnz_b, const in
                           const int32_t *rp_b, const int32_t *col_b, DevScratch &t, int32_t **m, int32_t **S,
                           int32_t **rp_c, uint64_t *nnz_c, hipStream_t s) {
     uint32_t *d_len = nullptr, *d_rpc = nullptr;
-    uint8_t *tmp = nullptr;
-    SUM_TRY(t.alloc(m, nnz_a));
-    SUM_TRY(t.alloc(S, nnz_a + 1));
-    SUM_TRY(t.alloc(&d_len, n_rows + 1));
-    SUM_TRY(t.alloc(&d_rpc, n_rows + 1));
+    DEV_TRY_RET(t.alloc(m, nnz_a));
+    DEV_TRY_RET(t.alloc(S, nnz_a + 1));
+    DEV_TRY_RET(t.alloc(&d_len, n_rows + 1));
+    DEV_TRY_RET(t.alloc(&d_rpc, n_rows + 1));
     *rp_c = reinterpret_cast<int32_t *>(d_rpc);
     if (nnz_a > 0 && nnz_b > 0) {
         const int64_t n_chunks = sum_chunks(nnz_a);
         hipLaunchKernelGGL(sum_match_kernel, dim3(sum_grid(n_chunks, 1)), dim3(kSumThreads), 0, s, (int32_t)n_rows, nnz_a,
                            n_chunks, rp_a, col_a, rp_b, col_b, *m);
-        SUM_TRY(hipGetLastError());
+        DEV_TRY_RET(hipGetLastError());
         hipcub::CountingInputIterator<int64_t> idx(0);
         hipcub::TransformInputIterator<int32_t, MatchFlag, hipcub::CountingInputIterator<int64_t>> in(idx, MatchFlag{*m, nnz_a});
-        size_t bytes = 0;
-        SUM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, *S, (int)(nnz_a + 1), s));
-        SUM_TRY(t.alloc(&tmp, (int64_t)bytes));
-        SUM_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, *S, (int)(nnz_a + 1), s));
+        DEV_TRY_RET(dev_excl_sum(t, in, *S, nnz_a + 1, s));
     } else {   // nothing can match: m[i] = ~rpB[row] = ~0 for every term of A (B is empty where A is not)
-        SUM_TRY(hipMemsetAsync(*m, 0xFF, (size_t)std::max<int64_t>(nnz_a, 1) * sizeof(int32_t), s));
-        SUM_TRY(hipMemsetAsync(*S, 0, (size_t)(nnz_a + 1) * sizeof(int32_t), s));
+        DEV_TRY_RET(hipMemsetAsync(*m, 0xFF, (size_t)std::max<int64_t>(nnz_a, 1) * sizeof(int32_t), s));
+        DEV_TRY_RET(hipMemsetAsync(*S, 0, (size_t)(nnz_a + 1) * sizeof(int32_t), s));
     }
     hipLaunchKernelGGL(sum_rows_kernel, dim3(sum_grid(n_rows + 1, kSumThreads)), dim3(kSumThreads), 0, s, n_rows, rp_a, rp_b, *S, d_len);
-    SUM_TRY(hipGetLastError());
-    size_t bytes = 0;
-    uint8_t *tmp2 = nullptr;
-    SUM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_len, d_rpc, (int)(n_rows + 1), s));
-    SUM_TRY(t.alloc(&tmp2, (int64_t)bytes));
-    SUM_TRY(hipcub::DeviceScan::ExclusiveSum(tmp2, bytes, d_len, d_rpc, (int)(n_rows + 1), s));
+    DEV_TRY_RET(hipGetLastError());
+    DEV_TRY_RET(dev_excl_sum(t, d_len, d_rpc, n_rows + 1, s));
     uint32_t total = 0;
-    SUM_TRY(hipMemcpyAsync(&total, d_rpc + n_rows, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    SUM_TRY(hipStreamSynchronize(s));
+    DEV_TRY_RET(hipMemcpyAsync(&total, d_rpc + n_rows, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DEV_TRY_RET(hipStreamSynchronize(s));
     *nnz_c = total;
     return hipSuccess;
 }

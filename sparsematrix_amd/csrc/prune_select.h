@@ -68,12 +68,6 @@ __global__ __launch_bounds__(kPThreads) void prune_pick_kernel(int pass, uint32_
     }
 }
 
-#define PR_TRY(x)                        \
-    do {                                 \
-        const hipError_t e_ = (x);       \
-        if (e_ != hipSuccess) return e_; \
-    } while (0)
-
 inline uint32_t float_key(float v) {
     uint32_t b;
     memcpy(&b, &v, 4);

@@ -12,11 +12,10 @@
 // steps of (255, T), sparse-matrix.cc:49-56), an exclusive scan places them, and one pass
 // writes the stream.  The codebook (when none is given): the values' distinct fp32 bit
 // patterns in first-occurrence order (a stable sort of (bits, index) and the run heads).
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstring>
 
+#include "devprim.h"
 #include "encode.h"
 #include "sm_internal.h"
 
@@ -143,19 +142,6 @@ __global__ __launch_bounds__(256) void refenc_panels_kernel(int64_t n_panels, in
     }
 }
 
-unsigned grid_for(int64_t n) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16));
-}
-
-#define RE_TRY(x)                   \
-    do {                            \
-        const hipError_t e_ = (x);  \
-        if (e_ != hipSuccess) {     \
-            err = e_;               \
-            return -5;              \
-        }                           \
-    } while (0)
-
 }  // namespace
 
 int encode_csr_ref_device(const int32_t *d_rp, const int32_t *d_col, const float *d_val, const uint8_t *d_ids,
@@ -181,32 +167,28 @@ int encode_csr_ref_device(const int32_t *d_rp, const int32_t *d_col, const float
     } else if (nnz > 0) {
         uint32_t *bits = nullptr, *bits_s = nullptr, *hb = nullptr;
         int32_t *idx = nullptr, *idx_s = nullptr, *nh = nullptr, *hi = nullptr;
-        RE_TRY(b.alloc(&bits, nnz));
-        RE_TRY(b.alloc(&bits_s, nnz));
-        RE_TRY(b.alloc(&idx, nnz));
-        RE_TRY(b.alloc(&idx_s, nnz));
-        RE_TRY(b.alloc(&nh, 1));
-        RE_TRY(b.alloc(&hb, 256));
-        RE_TRY(b.alloc(&hi, 256));
-        hipLaunchKernelGGL(refenc_bits_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, d_val, bits, idx);
-        RE_TRY(hipGetLastError());
-        size_t tmp_bytes = 0;
-        RE_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, bits, bits_s, idx, idx_s, (int)nnz, 0, 32, s));
-        uint8_t *tmp = nullptr;
-        RE_TRY(b.alloc(&tmp, (int64_t)tmp_bytes));
-        RE_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, bits, bits_s, idx, idx_s, (int)nnz, 0, 32, s));
-        RE_TRY(hipMemsetAsync(nh, 0, 4, s));
-        hipLaunchKernelGGL(refenc_heads_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, bits_s, idx_s, nh, hb, hi);
-        RE_TRY(hipGetLastError());
+        DEV_TRY(b.alloc(&bits, nnz));
+        DEV_TRY(b.alloc(&bits_s, nnz));
+        DEV_TRY(b.alloc(&idx, nnz));
+        DEV_TRY(b.alloc(&idx_s, nnz));
+        DEV_TRY(b.alloc(&nh, 1));
+        DEV_TRY(b.alloc(&hb, 256));
+        DEV_TRY(b.alloc(&hi, 256));
+        hipLaunchKernelGGL(refenc_bits_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, d_val, bits, idx);
+        DEV_TRY(hipGetLastError());
+        DEV_TRY(dev_sort_pairs(b, bits, bits_s, idx, idx_s, nnz, 32, s));
+        DEV_TRY(hipMemsetAsync(nh, 0, 4, s));
+        hipLaunchKernelGGL(refenc_heads_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, bits_s, idx_s, nh, hb, hi);
+        DEV_TRY(hipGetLastError());
         int32_t n_heads = 0;
-        RE_TRY(hipMemcpyAsync(&n_heads, nh, 4, hipMemcpyDeviceToHost, s));
-        RE_TRY(hipStreamSynchronize(s));
+        DEV_TRY(hipMemcpyAsync(&n_heads, nh, 4, hipMemcpyDeviceToHost, s));
+        DEV_TRY(hipStreamSynchronize(s));
         if (n_heads > (int32_t)kMaxStep) return -3;
         std::vector<uint32_t> hbits((size_t)n_heads);
         std::vector<int32_t> hidx((size_t)n_heads);
         if (n_heads) {
-            RE_TRY(hipMemcpy(hbits.data(), hb, (size_t)n_heads * 4, hipMemcpyDeviceToHost));
-            RE_TRY(hipMemcpy(hidx.data(), hi, (size_t)n_heads * 4, hipMemcpyDeviceToHost));
+            DEV_TRY(hipMemcpy(hbits.data(), hb, (size_t)n_heads * 4, hipMemcpyDeviceToHost));
+            DEV_TRY(hipMemcpy(hidx.data(), hi, (size_t)n_heads * 4, hipMemcpyDeviceToHost));
         }
         std::vector<int32_t> order((size_t)n_heads);
         for (int32_t i = 0; i < n_heads; i++) order[(size_t)i] = i;
@@ -255,69 +237,56 @@ int encode_csr_ref_device(const int32_t *d_rp, const int32_t *d_col, const float
     uint64_t *key = nullptr, *key_s = nullptr;
     int32_t *bad = nullptr;
     int64_t *bytes = nullptr, *off = nullptr, *pb = nullptr, *pe = nullptr;
-    RE_TRY(b.alloc(&d_tb, K));
-    RE_TRY(b.alloc(&d_tid, K));
-    RE_TRY(b.alloc(&ids, nnz));
-    RE_TRY(b.alloc(&ids_s, nnz));
-    RE_TRY(b.alloc(&key, nnz));
-    RE_TRY(b.alloc(&key_s, nnz));
-    RE_TRY(b.alloc(&bad, 1));
-    RE_TRY(hipMemcpyAsync(d_tb, tbits.data(), (size_t)K * 4, hipMemcpyHostToDevice, s));
-    RE_TRY(hipMemcpyAsync(d_tid, tids.data(), (size_t)K, hipMemcpyHostToDevice, s));
-    RE_TRY(hipMemsetAsync(bad, 0, 4, s));
+    DEV_TRY(b.alloc(&d_tb, K));
+    DEV_TRY(b.alloc(&d_tid, K));
+    DEV_TRY(b.alloc(&ids, nnz));
+    DEV_TRY(b.alloc(&ids_s, nnz));
+    DEV_TRY(b.alloc(&key, nnz));
+    DEV_TRY(b.alloc(&key_s, nnz));
+    DEV_TRY(b.alloc(&bad, 1));
+    DEV_TRY(hipMemcpyAsync(d_tb, tbits.data(), (size_t)K * 4, hipMemcpyHostToDevice, s));
+    DEV_TRY(hipMemcpyAsync(d_tid, tids.data(), (size_t)K, hipMemcpyHostToDevice, s));
+    DEV_TRY(hipMemsetAsync(bad, 0, 4, s));
     hipLaunchKernelGGL(refenc_keys_kernel, dim3(g_rows), dim3(256), 0, s, n_rows, d_rp, d_col, d_val, d_ids, d_tb,
                        d_tid, K, lin_bits, key, ids, bad);
-    RE_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     int32_t h_bad = 0;
-    RE_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
-    RE_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipStreamSynchronize(s));
     if (h_bad) return -2;
-    {
-        size_t tmp_bytes = 0;
-        const int end_bit = lin_bits + panel_bits;
-        RE_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, key, key_s, ids, ids_s, (int)nnz, 0, end_bit, s));
-        uint8_t *tmp = nullptr;
-        RE_TRY(b.alloc(&tmp, (int64_t)tmp_bytes));
-        RE_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, key, key_s, ids, ids_s, (int)nnz, 0, end_bit, s));
-    }
-    RE_TRY(b.alloc(&bytes, nnz));
-    RE_TRY(b.alloc(&off, nnz));
+    DEV_TRY(dev_sort_pairs(b, key, key_s, ids, ids_s, nnz, lin_bits + panel_bits, s));
+    DEV_TRY(b.alloc(&bytes, nnz));
+    DEV_TRY(b.alloc(&off, nnz));
     // `bad` is still 0 here (a value outside the codebook returned above): it now takes the repeats
-    hipLaunchKernelGGL(refenc_bytes_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, key_s, lin_bits, bytes, bad);
-    RE_TRY(hipGetLastError());
-    {
-        size_t tmp_bytes = 0;
-        RE_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, bytes, off, (int)nnz, s));
-        uint8_t *tmp = nullptr;
-        RE_TRY(b.alloc(&tmp, (int64_t)tmp_bytes));
-        RE_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, bytes, off, (int)nnz, s));
-    }
+    hipLaunchKernelGGL(refenc_bytes_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, key_s, lin_bits, bytes, bad);
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(dev_excl_sum(b, bytes, off, nnz, s));
     int64_t last[2] = {0, 0};
-    RE_TRY(hipMemcpyAsync(&last[0], off + nnz - 1, 8, hipMemcpyDeviceToHost, s));
-    RE_TRY(hipMemcpyAsync(&last[1], bytes + nnz - 1, 8, hipMemcpyDeviceToHost, s));
-    RE_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
-    RE_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipMemcpyAsync(&last[0], off + nnz - 1, 8, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipMemcpyAsync(&last[1], bytes + nnz - 1, 8, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipStreamSynchronize(s));
     if (h_bad) return -6;   // a repeated (row, column): no stream of the reference's holds it
     const int64_t total = last[0] + last[1];
     uint8_t *pos = nullptr, *vid = nullptr;
-    RE_TRY(b.alloc(&pos, total));
-    RE_TRY(b.alloc(&vid, total));
-    RE_TRY(b.alloc(&pb, n_panels));
-    RE_TRY(b.alloc(&pe, n_panels));
-    hipLaunchKernelGGL(refenc_emit_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, key_s, ids_s, lin_bits, off, T,
+    DEV_TRY(b.alloc(&pos, total));
+    DEV_TRY(b.alloc(&vid, total));
+    DEV_TRY(b.alloc(&pb, n_panels));
+    DEV_TRY(b.alloc(&pe, n_panels));
+    hipLaunchKernelGGL(refenc_emit_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, key_s, ids_s, lin_bits, off, T,
                        pos, vid);
-    RE_TRY(hipGetLastError());
-    hipLaunchKernelGGL(refenc_panels_kernel, dim3(grid_for(n_panels)), dim3(256), 0, s, n_panels, n_rows, d_rp, off,
+    DEV_TRY(hipGetLastError());
+    hipLaunchKernelGGL(refenc_panels_kernel, dim3(grid_of(n_panels)), dim3(256), 0, s, n_panels, n_rows, d_rp, off,
                        total, pb, pe);
-    RE_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     out.pos.resize((size_t)total);
     out.val_id.resize((size_t)total);
     std::vector<int64_t> hb((size_t)n_panels), he((size_t)n_panels);
-    RE_TRY(hipMemcpyAsync(out.pos.data(), pos, (size_t)total, hipMemcpyDeviceToHost, s));
-    RE_TRY(hipMemcpyAsync(out.val_id.data(), vid, (size_t)total, hipMemcpyDeviceToHost, s));
-    RE_TRY(hipMemcpyAsync(hb.data(), pb, (size_t)n_panels * 8, hipMemcpyDeviceToHost, s));
-    RE_TRY(hipMemcpyAsync(he.data(), pe, (size_t)n_panels * 8, hipMemcpyDeviceToHost, s));
-    RE_TRY(hipStreamSynchronize(s));
+    DEV_TRY(hipMemcpyAsync(out.pos.data(), pos, (size_t)total, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipMemcpyAsync(out.val_id.data(), vid, (size_t)total, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipMemcpyAsync(hb.data(), pb, (size_t)n_panels * 8, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipMemcpyAsync(he.data(), pe, (size_t)n_panels * 8, hipMemcpyDeviceToHost, s));
+    DEV_TRY(hipStreamSynchronize(s));
     for (int64_t p = 0; p < n_panels; p++) {   // panels with entries only (sparse-matrix.cc:57-61)
         if (he[(size_t)p] == hb[(size_t)p]) continue;
         out.panel_row_off.push_back(0);

@@ -27,19 +27,14 @@
 // order -- the same pack / sort / unpack with the widened id as the "value" (8 more bytes per
 // term of scratch; such matrices are bounded by their dense index).  transpose_terms_device: the
 // terms' own indices the same way (sm_build_opts.updatable: values given in the source's order).
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <vector>
 
+#include "devprim.h"
 #include "sm_internal.h"
 
 namespace smamd {
 namespace {
-
-unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
-
-#define GS_LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 __global__ __launch_bounds__(256) void tr_count_kernel(int64_t nnz, const int32_t *__restrict__ col,
                                                        int32_t *__restrict__ cnt) {
@@ -88,13 +83,8 @@ __global__ __launch_bounds__(256) void tr_narrow_kernel(int64_t nnz, const uint3
     GS_LOOP(j, nnz) ids[j] = (uint8_t)wide[j];
 }
 
-#define TR_TRY(x)                       \
-    do {                                \
-        const hipError_t e_ = (x);      \
-        if (e_ != hipSuccess) return e_; \
-    } while (0)
-
-int bits_for(uint32_t v) {   // 0 for v == 0
+// Bits that hold v, 0 for v == 0 (one column: no sort); devprim.h's bits_for counts at least 1.
+int key_bits(uint32_t v) {
     int b = 0;
     while (b < 32 && (v >> b) != 0) ++b;
     return b;
@@ -105,42 +95,38 @@ hipError_t transpose_body(const int32_t *rp, const int32_t *col, const float *va
     DevScratch t;
     if (t_rp) {   // (null with t_col: only the values' new order is wanted)
         int32_t *cnt = nullptr;
-        TR_TRY(t.alloc(&cnt, n_cols + 1));
-        TR_TRY(hipMemsetAsync(cnt, 0, (size_t)(n_cols + 1) * 4, s));
+        DEV_TRY_RET(t.alloc(&cnt, n_cols + 1));
+        DEV_TRY_RET(hipMemsetAsync(cnt, 0, (size_t)(n_cols + 1) * 4, s));
         if (nnz > 0) {
             hipLaunchKernelGGL(tr_count_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, col, cnt);
-            TR_TRY(hipGetLastError());
+            DEV_TRY_RET(hipGetLastError());
         }
-        size_t bytes = 0;
-        TR_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, t_rp, (int)(n_cols + 1), s));
-        uint8_t *tmp = nullptr;
-        TR_TRY(t.alloc(&tmp, (int64_t)bytes));
-        TR_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, t_rp, (int)(n_cols + 1), s));
+        DEV_TRY_RET(dev_excl_sum(t, cnt, t_rp, n_cols + 1, s));
     }
     if (nnz > 0) {
         uint32_t *key[2] = {nullptr, nullptr};
         unsigned long long *word[2] = {nullptr, nullptr};
-        const int end_bit = bits_for((uint32_t)(n_cols - 1));
-        TR_TRY(t.alloc(&key[0], nnz));
-        TR_TRY(t.alloc(&word[0], nnz));
+        const int end_bit = key_bits((uint32_t)(n_cols - 1));
+        DEV_TRY_RET(t.alloc(&key[0], nnz));
+        DEV_TRY_RET(t.alloc(&word[0], nnz));
         hipLaunchKernelGGL(tr_pack_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, (int32_t)n_rows, rp, col, val,
                            key[0], word[0]);
-        TR_TRY(hipGetLastError());
+        DEV_TRY_RET(hipGetLastError());
         const unsigned long long *sorted = word[0];   // one column: every key equal, stored order stays
         if (end_bit > 0) {
-            TR_TRY(t.alloc(&key[1], nnz));
-            TR_TRY(t.alloc(&word[1], nnz));
+            DEV_TRY_RET(t.alloc(&key[1], nnz));
+            DEV_TRY_RET(t.alloc(&word[1], nnz));
             hipcub::DoubleBuffer<uint32_t> dk(key[0], key[1]);
             hipcub::DoubleBuffer<unsigned long long> dw(word[0], word[1]);
             size_t bytes = 0;
-            TR_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, dk, dw, (int)nnz, 0, end_bit, s));
+            DEV_TRY_RET(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, dk, dw, (int)nnz, 0, end_bit, s));
             uint8_t *tmp = nullptr;
-            TR_TRY(t.alloc(&tmp, (int64_t)bytes));
-            TR_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, dk, dw, (int)nnz, 0, end_bit, s));
+            DEV_TRY_RET(t.alloc(&tmp, (int64_t)bytes));
+            DEV_TRY_RET(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, dk, dw, (int)nnz, 0, end_bit, s));
             sorted = dw.Current();
         }
         hipLaunchKernelGGL(tr_unpack_kernel, dim3(grid_of(nnz)), dim3(256), 0, s, nnz, sorted, t_col, t_val);
-        TR_TRY(hipGetLastError());
+        DEV_TRY_RET(hipGetLastError());
     }
     return hipStreamSynchronize(s);   // the scratch is freed on return
 }

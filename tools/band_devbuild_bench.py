@@ -1,5 +1,6 @@
 """Build times of config 2's balanced bands, device builder (builddev_band2.hip) against host
-builder (band2.cpp), for from_csr on device tensors and for transposed(): the figures of
+builder (band2.cpp), and of the gathered chunk bands forced on the same input (builddev_gcb.hip
+against gcb.cpp), for from_csr on device tensors and for transposed(): the figures of
 profiles/band_devbuild.txt.  Usage: python tools/band_devbuild_bench.py"""
 import os
 import statistics
@@ -36,7 +37,9 @@ def stats(v):
 say("device:", torch.cuda.get_device_name(0))
 say("config 2: 2^20 x 2^20, 16 per row (synth.uniform_rows_device, seed 5); wall clock of the call between")
 say("device synchronisations; host_build 0 and 1 alternate in one process; 1 untimed warm-up pair first")
-for enc in ("cband (255-value codebook, AUTO)", "band2 (uniform fp32 values, AUTO)"):
+CASES = (("cband (255-value codebook, AUTO)", {}), ("band2 (uniform fp32 values, AUTO)", {}),
+         ("gcb (255-value codebook, layout gcb)", dict(layout="gcb")))
+for enc, lay in CASES:
     rp, ci, va = synth.uniform_rows_device(n, n, 16, seed=5)
     if enc.startswith("band2"):
         va = torch.rand(va.numel(), device="cuda", generator=torch.Generator(device="cuda").manual_seed(9)) * 2 - 1
@@ -45,17 +48,16 @@ for enc in ("cband (255-value codebook, AUTO)", "band2 (uniform fp32 values, AUT
     keep = None
     for rep in range(6):
         for hb in (0, 1):
-            M, dt = timed(lambda: sm.SparseMatrix.from_csr(rp, ci, va, n, opts=dict(host_build=hb)))
+            M, dt = timed(lambda: sm.SparseMatrix.from_csr(rp, ci, va, n, opts=dict(lay, host_build=hb)))
             if rep:
                 t[hb].append(dt)
             else:
-                say(f"  {enc}: host_build={hb} has_xband={M.info()['has_xband']} bands={M.info()['xband_bands']} "
-                    f"built_on_device={M.built_on_device()} digest={M.layout_digest()}")
+                say(f"  {enc}: host_build={hb} has_xband={M.info()['has_xband']} bands={M.info()['xband_bands']} "                    f"built_on_device={M.built_on_device()} digest={M.layout_digest()}")
             if hb == 0:
                 keep = M
     for rep in range(6):
         for hb in (0, 1):
-            T, dt = timed(lambda: keep.transposed(opts=dict(host_build=hb)))
+            T, dt = timed(lambda: keep.transposed(opts=dict(lay, host_build=hb)))
             if rep:
                 tt[hb].append(dt)
             else:
