@@ -93,8 +93,32 @@ typedef enum sm_trans { SM_NO_TRANS = 0, SM_TRANS = 1 } sm_trans;
 typedef enum sm_algo {
     SM_ALGO_AUTO = 0,     /* band layout if built, else sell, else stream (SpMV); row-panel (SpMM) */
     SM_ALGO_PARITY = 1,   /* bit-exact with the reference for every row            */
-    SM_ALGO_STREAM = 2,   /* nnz-balanced row tiles through LDS (+ long-row split) */
-    SM_ALGO_VECTOR = 3,   /* L lanes per row (CSR-vector), shuffle reduction       */
+    SM_ALGO_STREAM = 2,   /* nnz-balanced row tiles through LDS (+ long-row split).  One fixed
+                             order per row, every operation rounded separately, a term being
+                             t = fl(x[c] * fl(v * alpha)) and by = fl(beta * y) (y itself when
+                             beta == 1):
+                             - a row of <= SM_SERIAL_ROW_MAX terms: by, then its terms in stored
+                               order (the reference's bits);
+                             - a longer row of <= tile_nnz terms: lane l of 64 adds the row's
+                               terms l, l + 64, ... from +0.0, the lane sums are added in an
+                               xor tree at lane distances 32 .. 1, y = fl(by + that);
+                             - a row of more than tile_nnz terms (sm_info.n_long_rows counts
+                               them) is cut into chunks of 4096 terms from its first term.  In
+                               a chunk [begin, end), thread t of 256 adds the term indices
+                               (begin & ~3) + 4 t + q + 1024 j, q = 0 .. 3, j = 0, 1, ..., that
+                               lie in the chunk, ascending, from +0.0; each wavefront's 64 sums
+                               go through the same xor tree; wavefronts 0 .. 3 are added in
+                               order; the chunk sums are added onto by in chunk order.
+                             So a row's bits depend on tile_nnz only through which of the last
+                             two cases it falls in: sm_build_opts.tile_nnz changes the bits of
+                             the rows whose length lies between two sizes, and of no other row.
+                             Deterministic; every row within the sum|terms| bound.            */
+    SM_ALGO_VECTOR = 3,   /* L lanes per row (CSR-vector), L = the first of 2, 4, .. 64 that is
+                             not below nnz / n_rows: lane l adds the row's terms l, l + L, ...
+                             from +0.0 (terms as for STREAM), the L sums are added in an xor tree
+                             at lane distances L/2 .. 1, y = fl(by + that) -- for every row, so a
+                             row without terms ends as fl(by + 0.0) (+0.0 where by is -0.0).
+                             Deterministic; every row within the sum|terms| bound.            */
     SM_ALGO_XBAND = 4,    /* x staged through LDS in column bands (the layout built at
                              creation, see sm_info.has_xband); falls back to SELL, then
                              STREAM, when the matrix holds no band layout             */
@@ -283,7 +307,14 @@ typedef struct sm_build_opts {
     int32_t sell_streams;      /* XCD streams of sort windows, 0 = auto                */
     int64_t sell_sigma;        /* sort rows by length within windows of this many rows, 0 = globally */
     int32_t relabel;           /* column relabeling by degree: -1 auto, 0 never, 1 always */
-    int32_t tile_nnz;          /* stream-kernel tile: 1024/2048/4096/8192, 0 = auto   */
+    int32_t tile_nnz;          /* stream-kernel tile: 1024/2048/4096/8192 terms; 0 = auto: 4096, or
+                                  2048 when the longest row exceeds 64 x the mean row length;
+                                  any other value is SM_ERR_INVALID_ARG.  A tile takes rows, in
+                                  order, while it holds <= tile_nnz terms and <= 1024 rows
+                                  (sm_info.n_tiles); a row of more than tile_nnz terms is a long
+                                  row, summed in chunks across workgroups (sm_info.n_long_rows).
+                                  The size therefore changes SM_ALGO_STREAM's bits for the rows
+                                  longer than one size and not the other (see SM_ALGO_STREAM)  */
     int32_t ccsell;            /* column-chunked sliced-ELL (wide x): -1 auto, 0 never, 1 always
                                   (where no band layout is built and it applies)       */
     int32_t ccsell_chunk_log2; /* its column chunk, log2 columns (8..24), 0 = 20 (4 MiB of x) */

@@ -11,7 +11,8 @@ pieces, the sweep's 256-row blocks, kSellGroup = 4 slices of 64 rows, ccsell chu
 columns); 300 x 513 / 767 / 768 (three slabs whose last is 1, 255 and 256 columns wide).  The
 2048-term constants (kSellMaxLen, kCcMaxUnit, the stream kernel's tile) and the 4096 / 8192 /
 16384 ones (row blocks, x windows) lie above every shape here: their edges are the long-row
-cases of layout_specs.py and the ragged cases of test_gpu_devbuild*.py.
+cases of layout_specs.py and the ragged cases of test_gpu_devbuild*.py; the stream kernel's
+tile (every size, at T - 1 / T / T + 1 terms) is the subject of stream_ref.py.
 
 Patterns (rows strictly ascending, no RNG in the structure so that small_grid.h restates it
 exactly):
